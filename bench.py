@@ -10,6 +10,12 @@ evaluation and runs before the timed region, sharded over ranks + RCCL all-gathe
 
     python bench.py [--gpus N] [--steps K] [--warmup W]            (N > 1: spawns the N ranks itself, see launch_ranks)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                                     (+ every measurement and check beside the headline)
+    python bench.py ... --dump-outputs DIR                         (+ the last timed step's outputs as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what needs runs of its own: the warm
+update_classifier, the unblocked host time, power / clock samples, the roofline pass, the PCIe-inclusive leg, the CPU
+baseline + parity against the oracle, the multi-rank self-check (dp_check), the host probe and the secondary configs.
 
 Prints ONE JSON line (rank 0) - see DESIGN.md "Measurement" for how each field is obtained.
 """
@@ -67,6 +73,24 @@ def launch_ranks(argv, n: int) -> int:
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy (float32 / float64 only, at most DUMP_LIMIT_BYTES in all), so that two
+    builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    log(f"[bench] outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in arrays.items()))
 
 
 def _timed(fn):
@@ -322,10 +346,10 @@ HOST_PROBE_SHARE = 8
 
 
 def run_secondary(args_extra, timeout_s: int, env_extra=None, keep_extra=()):
-    """One of the other BASELINE configs as a CHILD process of this (finished) measurement: `python bench.py <args> --secondary`;
+    """One of the other BASELINE configs as a CHILD process of this (finished) measurement: `python bench.py <args> --full --secondary`;
     its single JSON line, reduced to the fields a reader needs.  Never raises: a failure is reported in place."""
     import subprocess
-    cmd = [sys.executable, str(Path(__file__).resolve())] + args_extra + ["--secondary"]
+    cmd = [sys.executable, str(Path(__file__).resolve())] + args_extra + ["--full", "--secondary"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update(env_extra or {})
     t0 = time.time()
@@ -419,8 +443,14 @@ def train_mode(a, model, cfg, h, rank, world, group, ranks_seen, dev, real_stdou
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        # what the last step hands its caller: the loss, and the weights it left behind (a fixed, seeded sample of the flat fp32 buffer)
+        n_ = opt.flat.numel()
+        pick = torch.randint(0, n_, (min(n_, 1 << 20),), generator=torch.Generator().manual_seed(0)).sort().values.to(dev)
+        dump_outputs(a.dump_outputs, {"loss": np.array([float(loss)], dtype=np.float64),
+                                      "weights_sample": opt.flat[pick].cpu().numpy(), "weights_sample_index": pick.cpu().numpy().astype(np.float64)})
     dp_check = None
-    if world > 1:
+    if world > 1 and a.full:
         # self-check of the data-parallel step (first real N > 1 run): after the overlapped all-reduce every rank holds the SAME
         # summed gradient buffer and, after the fused clip + AdamW, the same weights; every rank drew the same negatives.  The
         # per-rank loss is the mean CE over that rank's shard of the global batch: it legitimately differs, all of them are listed.
@@ -448,7 +478,7 @@ def train_mode(a, model, cfg, h, rank, world, group, ranks_seen, dev, real_stdou
     picks = model._trainer.last_contra
     uniq = len({i for ids, _ in picks for i in ids})
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         # the oracle's OM step (oracle/train_ref.py: fp32 autograd over the functional towers, pinned by the reference's train_batch
         # fixtures) on a REDUCED batch with this step's own negatives, once, at the thread count that runs its image tower fastest.
         # The text-tower passes (len(picks) x <= 257 prompts) do not shrink with the batch, so this UNDER-states the CPU's rate at the
@@ -529,6 +559,10 @@ def main():
     ap.add_argument("--secondary", dest="is_secondary", action="store_true", help="(internal) this process IS a secondary child: no grandchildren")
     ap.add_argument("--no-host-probe", dest="host_probe", action="store_false", help="default run only: skip the multi-process host-time probe")
     ap.add_argument("--no-power-probe", dest="power_probe", action="store_false", help="skip the rocm-smi power / clock samples taken over extra steps behind the timed region")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beside the headline (warm update_classifier, "
+                    "unblocked host time, power probe, roofline pass, PCIe leg, CPU baseline + parity, dp_check, host probe, secondary configs); "
+                    "the --no-* switches above act within it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     a = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -618,19 +652,23 @@ def main():
     model.update_classifier(group=group)
     torch.cuda.synchronize()
     t_uc_first = time.time() - t0
-    # once more, warm (prepared weights and workspace exist): what the one-off costs a rank - with N > 1 its own shard of the prompts
-    # plus the all-gather of the class rows (hgr_net_amd.parallel.sharded_text_features)
-    if group is not None:
-        import torch.distributed as dist
-        dist.barrier()
-    t0 = time.time()
-    model.update_classifier(group=group)
-    torch.cuda.synchronize()
-    t_uc = time.time() - t0
-    uc_all = _gather_obj(round(t_uc, 4), world) if world > 1 else [round(t_uc, 4)]
-    uc_info = {"s_per_rank_max": max(uc_all), "s_per_rank_min": min(uc_all), "first_call_s": round(t_uc_first, 2), "prompts_per_rank": -(-a.nodes // world),
-               "how": "second (warm) call of update_classifier: text tower over this rank's shard of the N prompts" + (" + all-gather of the class rows" if world > 1 else "") + "; one-off per evaluation, outside the timed region"}
-    log(f"[bench] update_classifier (text tower, {a.nodes} prompts, one-off, untimed): first {t_uc_first:.2f}s, warm {t_uc:.3f}s")
+    uc_info = {"first_call_s": round(t_uc_first, 2), "prompts_per_rank": -(-a.nodes // world)}
+    if a.full:
+        # once more, warm (prepared weights and workspace exist): what the one-off costs a rank - with N > 1 its own shard of the prompts
+        # plus the all-gather of the class rows (hgr_net_amd.parallel.sharded_text_features)
+        if group is not None:
+            import torch.distributed as dist
+            dist.barrier()
+        t0 = time.time()
+        model.update_classifier(group=group)
+        torch.cuda.synchronize()
+        t_uc = time.time() - t0
+        uc_all = _gather_obj(round(t_uc, 4), world) if world > 1 else [round(t_uc, 4)]
+        uc_info = {"s_per_rank_max": max(uc_all), "s_per_rank_min": min(uc_all), **uc_info,
+                   "how": "second (warm) call of update_classifier: text tower over this rank's shard of the N prompts" + (" + all-gather of the class rows" if world > 1 else "") + "; one-off per evaluation, outside the timed region"}
+        log(f"[bench] update_classifier (text tower, {a.nodes} prompts, one-off, untimed): first {t_uc_first:.2f}s, warm {t_uc:.3f}s")
+    else:
+        log(f"[bench] update_classifier (text tower, {a.nodes} prompts, one-off, untimed): {t_uc_first:.2f}s")
     model.zsl_unplanted = model.zsl_weights
     # the planted rows are those of EVERY rank's step targets, so that all ranks evaluate against the same class matrix
     all_targets = [te[(7 * i + r) % len(te)] for r in range(world) for i in range(a.steps + a.warmup)]
@@ -672,46 +710,64 @@ def main():
     elapsed_local = elapsed
     step_ms = step_time_stats(marks)
     host_ms_loop = host_s / a.steps * 1e3
-    # ... inside the loop that figure includes BACK-PRESSURE: a HIP graph cannot be launched again while its previous replay is running,
-    # and the steps alternate two graph pairs - the host runs at most two steps ahead and then waits in hipGraphLaunch, so in steady
-    # state it reads ~ms_per_step whatever the host's own cost is.  The host's own cost: pairs of steps (one of each parity) behind
-    # a fence, when nothing blocks
-    host_free = []
-    fence()
-    acc_keep = ev.acc.clone()                  # (these extra steps must not enter the counters the line and dp_check report)
-    for rep in range(4):
-        fence()
-        th = time.perf_counter()
-        step(a.warmup + (2 * rep) % a.steps)
-        step(a.warmup + (2 * rep + 1) % a.steps)
-        host_free.append((time.perf_counter() - th) / 2 * 1e3)
-    fence()
     if hasattr(model, "join_tail"):
         model.join_tail()
-    torch.cuda.synchronize()
-    power = None
-    if world == 1 and a.power_probe:           # (one rank only: the extra steps are not matched on other ranks)
-        power = power_probe(lambda i: step(a.warmup + i % a.steps), fence)
+    if a.dump_outputs:
+        # the counters every step advanced (all-reduced with N > 1: every rank takes part), then the last timed step once more with the
+        # outputs its caller can ask for - same batch, same target, same class matrix - its counter increments taken back out
+        counters = ev.counters(group)
+        acc_keep = ev.acc.clone()
+        j = a.warmup + a.steps - 1
+        if fused_eval:
+            pred, path = ev.add_images(batches[j & 1], targets[j], want_outputs=True)
+        else:
+            pred, path = ev.add_batch(model(batches[j & 1], None, static_output=True), targets[j])
+        ev.acc.copy_(acc_keep)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"pred_top20": pred.float().cpu().numpy(), "dict_path": path.float().cpu().numpy(),
+                                          "counters": np.array([counters[k] for k in evaluate.COUNTERS], dtype=np.float64)})
+    host_ms = power = None
+    if a.full:
+        # ... inside the loop that figure includes BACK-PRESSURE: a HIP graph cannot be launched again while its previous replay is running,
+        # and the steps alternate two graph pairs - the host runs at most two steps ahead and then waits in hipGraphLaunch, so in steady
+        # state it reads ~ms_per_step whatever the host's own cost is.  The host's own cost: pairs of steps (one of each parity) behind
+        # a fence, when nothing blocks
+        host_free = []
+        fence()
+        acc_keep = ev.acc.clone()                  # (these extra steps must not enter the counters the line and dp_check report)
+        for rep in range(4):
+            fence()
+            th = time.perf_counter()
+            step(a.warmup + (2 * rep) % a.steps)
+            step(a.warmup + (2 * rep + 1) % a.steps)
+            host_free.append((time.perf_counter() - th) / 2 * 1e3)
+        fence()
         if hasattr(model, "join_tail"):
             model.join_tail()
         torch.cuda.synchronize()
-    ev.acc.copy_(acc_keep)
-    host_ms = sorted(host_free)[len(host_free) // 2]
+        if world == 1 and a.power_probe:           # (one rank only: the extra steps are not matched on other ranks)
+            power = power_probe(lambda i: step(a.warmup + i % a.steps), fence)
+            if hasattr(model, "join_tail"):
+                model.join_tail()
+            torch.cuda.synchronize()
+        ev.acc.copy_(acc_keep)
+        host_ms = sorted(host_free)[len(host_free) // 2]
     if world > 1:
         import torch.distributed as dist
-        t = torch.tensor([elapsed, host_ms, host_ms_loop], dtype=torch.float64, device=dev)
+        t = torch.tensor([elapsed, host_ms or 0.0, host_ms_loop], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, host_ms, host_ms_loop = float(t[0].item()), float(t[1].item()), float(t[2].item())
+        elapsed, host_ms_loop = float(t[0].item()), float(t[2].item())
+        host_ms = float(t[1].item()) if host_ms is not None else None
     ms = elapsed / a.steps * 1e3
     value = a.batch * world * a.steps / elapsed
-    dp_check = dp_check_eval(model, ev, group, world, rank, elapsed_local, a.steps, dev) if world > 1 else None
+    dp_check = dp_check_eval(model, ev, group, world, rank, elapsed_local, a.steps, dev) if world > 1 and a.full else None
     summary = ev.summary(group)
 
     # roofline of the dominant kernel (gemm_nt_128, the tower GEMMs): algorithmic FLOPs of every launch
     # (2*M*N*K) / that launch's duration, from HIP events recorded on the launch stream around each call
     # in a second, instrumented pass over the same steps (events perturb the timed pass, so it is separate).
     roof = None
-    if rank == 0:
+    if rank == 0 and a.full:
         ops.PROFILE = []
         graph_mode, model.use_graph = model.use_graph, False     # per-launch events need eager launches (a replayed graph has no host calls)
         for i in range(min(a.steps, 5)):
@@ -833,7 +889,7 @@ def main():
     # JPEG decoder hands over), H2D on a copy stream double-buffered against compute, normalisation fused into the
     # patch kernel (hgr_im2col_patches_u8).
     pcie = None
-    if a.pcie and cfg["vision_patch_size"]:
+    if a.full and a.pcie and cfg["vision_patch_size"]:
         r = cfg["image_resolution"]
         g = torch.Generator().manual_seed(1234 + rank)
         host = [torch.randint(0, 256, (a.batch, r, r, 3), dtype=torch.uint8, generator=g).pin_memory() for _ in range(2)]
@@ -879,7 +935,7 @@ def main():
                 "input": f"uint8 NHWC crops in pinned host memory ({a.batch * r * r * 3 / 1e6:.0f} MB/batch), H2D double-buffered on a copy stream"}
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         from oracle import tree_ref
         cpu = cpu_baseline(sd, model.zsl_weights.float().cpu(), arch=a.arch, c1=a.c1)
         # the metric's parity clause at full size, on the oracle's batch (same weights, same - planted - class matrix):
@@ -993,7 +1049,7 @@ def main():
                 "ms_per_step": round(ms, 3), "step_ms": step_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                 # max over ranks: what one rank's host thread spends per step when nothing blocks it (Python + two graph launches + Evaluator
                 # bookkeeping; median of 4 unblocked pairs) / the same inside the timed loop, where graph re-launch back-pressure is included
-                "host_ms_per_step": round(host_ms, 3), "host_ms_per_step_in_loop": round(host_ms_loop, 3),
+                "host_ms_per_step": round(host_ms, 3) if host_ms is not None else None, "host_ms_per_step_in_loop": round(host_ms_loop, 3),
                 "dtype": a.image_dtype, "data": "synthetic",
                 "config": {"arch": a.arch, "nodes": a.nodes, "batch_per_gpu": a.batch, "embed_dim": cfg["embed_dim"],
                            "workload": f"{a.arch} zero-shot eval step: encode_image + L2 + [{a.batch}x{cfg['embed_dim']}]x[{cfg['embed_dim']}x{a.nodes}] logits "
@@ -1009,7 +1065,7 @@ def main():
             line["dp_check"] = dp_check
             if not dp_check["ok"]:
                 log(f"[bench] dp_check FAILED: {json.dumps(dp_check)}")
-        default_run = a.arch == ARCH and a.batch == BATCH and a.nodes == N_NODES and world == 1 and group is None
+        default_run = a.full and a.arch == ARCH and a.batch == BATCH and a.nodes == N_NODES and world == 1 and group is None
         if a.host_probe and not a.is_secondary and default_run:
             # 8-GPU readiness that one GPU can show: the per-rank HOST cost of a step with several ranks' processes sharing the box's
             # cores (an 8-GPU node runs 8 of these next to each other; what caps weak scaling is a host that cannot keep 8 queues

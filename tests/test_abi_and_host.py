@@ -216,13 +216,11 @@ def test_world_size_2_gloo_sharding(tmp_path):
 
 
 def test_tokenizer_matches_reference_ids(golden_dir):
-    """BPE ids captured from the reference's tokenizer (tools/make_golden_tokenizer.py -> tests/golden/tokenizer_ids.json).
-    Needs the user's merges file; skipped where it is absent (it is reference data, not shipped)."""
+    """BPE ids captured from the reference's tokenizer (tools/make_golden_tokenizer.py -> tests/golden/tokenizer_ids.json), encoded
+    with the merges it reads (tests/golden/bpe_merges.txt.gz, same tool; HGR_BPE_VOCAB points at another copy of the merges file)."""
     from hgr_net_amd.clip import simple_tokenizer as st
     import os
-    path = os.environ.get("HGR_BPE_VOCAB") or "/root/reference/clip/bpe_simple_vocab_16e6.txt.gz"   # build container only
-    if not os.path.isfile(path):
-        pytest.skip("BPE merges file not available (set HGR_BPE_VOCAB)")
+    path = os.environ.get("HGR_BPE_VOCAB") or str(golden_dir / "bpe_merges.txt.gz")
     os.environ["HGR_BPE_VOCAB"] = path
     tok = st.SimpleTokenizer(path)
     gold = json.load(open(golden_dir / "tokenizer_ids.json"))

@@ -37,7 +37,7 @@ def _bench(n, extra):
 def test_two_ranks_complete_and_report_the_job():
     """1 rank and 2 ranks (torch.distributed.run, as the driver launches it): both finish, exactly one JSON line from
     rank 0, same keys, n_gpus / global batch / parallelism describe the whole job."""
-    common = ["--steps", "8", "--warmup", "2", "--nodes", "3000", "--batch", "32", "--arch", "small-vit", "--no-cpu-baseline", "--no-pcie"]
+    common = ["--steps", "8", "--warmup", "2", "--nodes", "3000", "--batch", "32", "--arch", "small-vit", "--no-cpu-baseline", "--no-pcie", "--full"]
     one = subprocess.run([sys.executable, str(ROOT / "bench.py")] + common, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][0])
@@ -57,7 +57,7 @@ def test_two_ranks_complete_and_report_the_job():
 def test_two_rank_training_bench_verifies_itself():
     """`bench.py --mode train` on two ranks: the JSON line carries dp_check (gradient buffer and weights identical on both ranks
     after the overlapped all-reduce + fused AdamW, same negatives), and the run exits 0 only when it holds."""
-    d = _bench(2, ["--mode", "train", "--arch", "small-vit", "--nodes", "3000", "--batch", "8", "--steps", "2", "--warmup", "1"])
+    d = _bench(2, ["--mode", "train", "--arch", "small-vit", "--nodes", "3000", "--batch", "8", "--steps", "2", "--warmup", "1", "--full"])
     c = d["dp_check"]
     assert c["ok"] and c["ranks_seen"] == 2 and c["grad_buffer_checksum_equal"] and c["weights_checksum_equal"] and c["negatives_equal"], c
     assert len(c["loss_per_rank"]) == 2 and d["n_gpus"] == 2
@@ -183,13 +183,13 @@ def test_many_rank_bench_control_flow_on_one_gpu():
     the default is 4 ranks on class / prompt counts that 4 does not divide; HGR_TEST_MAX_RANKS=8 runs the full eight where nothing
     limits it."""
     n = int(os.environ.get("HGR_TEST_MAX_RANKS", "4"))
-    d = _bench(n, ["--steps", "3", "--warmup", "1", "--nodes", "1003", "--batch", "8", "--arch", "small-vit", "--no-cpu-baseline", "--no-pcie"])
+    d = _bench(n, ["--steps", "3", "--warmup", "1", "--nodes", "1003", "--batch", "8", "--arch", "small-vit", "--no-cpu-baseline", "--no-pcie", "--full"])
     c = d["dp_check"]
     assert d["n_gpus"] == n and d["ranks_seen"] == n and d["config"]["parallelism"] == f"dp{n}" and d["config"]["global_batch"] == 8 * n
     assert c["ok"] and c["ranks_seen"] == n and c["zsl_checksum_equal"] and c["counters_allreduce_equals_sum_of_ranks"], c
     assert len(c["num_sample_per_rank"]) == n and sum(c["num_sample_per_rank"]) == n * (3 + 1) * 8, c
     # and one sharded training step per rank count: the prompt shards of `n` ranks over a prompt list that does not divide evenly
-    t = _bench(n, ["--mode", "train", "--arch", "small-vit", "--nodes", "1003", "--batch", "2", "--steps", "1", "--warmup", "1"])
+    t = _bench(n, ["--mode", "train", "--arch", "small-vit", "--nodes", "1003", "--batch", "2", "--steps", "1", "--warmup", "1", "--full"])
     assert t["dp_check"]["ok"] and t["dp_check"]["negatives_equal"] and t["n_gpus"] == n, t["dp_check"]
 
 
@@ -259,7 +259,7 @@ def test_bench_launches_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--nodes", "2000", "--batch", "16",
-                        "--arch", "small-vit", "--no-cpu-baseline", "--no-pcie"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--arch", "small-vit", "--no-cpu-baseline", "--no-pcie", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     if p.returncode != 0 and any(w in p.stderr for w in ("Address already in use", "RendezvousConnectionError", "DistNetworkError")):
         pytest.skip("could not set up a local rendezvous on this box")
     assert p.returncode == 0, p.stderr[-2000:]

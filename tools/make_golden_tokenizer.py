@@ -3,7 +3,8 @@
 with its own merges file bpe_simple_vocab_16e6.txt.gz) in this container on a fixed list of texts.  `ftfy` is absent
 here; the stand-in is the identity, which is what ftfy.fix_text does on these inputs (no mojibake in them).  Nothing of
 the reference travels: the fixture holds the input strings and the ids they encode to (SOT / EOT / padding are added by
-clip.tokenize and are not part of it)."""
+clip.tokenize and are not part of it).  Beside it, tests/golden/bpe_merges.txt.gz: the part of that merges file the tokenizer
+reads (its header line + the first 49152 - 256 - 2 merges), data for the tokenizer test, which then needs no reference checkout."""
 import importlib.util
 import json
 import os
@@ -23,7 +24,17 @@ TEXTS = ["a photo of a great white shark.", "a photo of a kind12 thing3.", "Hell
          "THE QUICK brown_fox jumps"]
 
 
+def write_merges():
+    import gzip
+    lines = gzip.open(REF / "clip" / "bpe_simple_vocab_16e6.txt.gz").read().decode("utf-8").split("\n")[:49152 - 256 - 2 + 1]
+    path = REPO / "tests" / "golden" / "bpe_merges.txt.gz"
+    with open(path, "wb") as f, gzip.GzipFile(filename="", fileobj=f, mode="wb", compresslevel=9, mtime=0) as g:
+        g.write(("\n".join(lines) + "\n").encode("utf-8"))
+    print("written", path)
+
+
 def main():
+    write_merges()
     install_stubs()
     spec = importlib.util.spec_from_file_location("ref_simple_tokenizer", REF / "clip" / "simple_tokenizer.py")
     mod = importlib.util.module_from_spec(spec)

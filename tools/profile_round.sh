@@ -3,8 +3,8 @@
 #
 #   gpurun --timeout 1100 -- 'bash tools/profile_round.sh r02_a'
 #
-# 1. plain `bench.py` (the bench line),
-# 2. `rocprofv3 --kernel-trace --stats -- python3 bench.py` (per-kernel time; its own bench line is kept beside it),
+# 1. `bench.py --full` (the bench line with every measurement beside the headline),
+# 2. `rocprofv3 --kernel-trace --stats -- python3 bench.py --full` (per-kernel time; its own bench line is kept beside it),
 # 3. two PMC passes of the same command, kernel-trace only (FETCH_SIZE and WRITE_SIZE do not fit one pass; --pmc is never
 #    combined with --stats / sys traces on this pool),
 # 4. tools/pmc_summary.py -> profiles/<tag>_pmc_summary.json, stamped with the kernel-source hash bench.py checks.
@@ -18,17 +18,17 @@ mkdir -p "$OUT" "$ROOT/profiles"
 export TMPDIR=/tmp
 cd /tmp
 
-python3 "$ROOT/bench.py" $ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 "$ROOT/bench.py" --full $ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "[profile] bench done: $(cut -c1-200 "$OUT/bench.json")"
 
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o "$TAG" -- python3 "$ROOT/bench.py" $ARGS --no-cpu-baseline --no-pcie --no-secondary --no-host-probe --no-power-probe \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o "$TAG" -- python3 "$ROOT/bench.py" --full $ARGS --no-cpu-baseline --no-pcie --no-secondary --no-host-probe --no-power-probe \
     > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof_stats.err"
 echo "[profile] kernel-trace stats done"
 
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o fetch -- python3 "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-pcie --no-secondary --no-host-probe --no-power-probe \
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o fetch -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-pcie --no-secondary --no-host-probe --no-power-probe \
     > /dev/null 2> "$OUT/rocprof_fetch.err"
 echo "[profile] FETCH_SIZE pass done"
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o write -- python3 "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-pcie --no-secondary --no-host-probe --no-power-probe \
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o write -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-pcie --no-secondary --no-host-probe --no-power-probe \
     > /dev/null 2> "$OUT/rocprof_write.err"
 echo "[profile] WRITE_SIZE pass done"
 
@@ -43,10 +43,10 @@ cp "$OUT/bench_under_rocprof.json" "$ROOT/profiles/${TAG}_vitb32_bench_under_roc
 # OM training step): kernel-trace statistics and the two PMC passes of each (PROFILE_SECONDARY=0 skips them)
 profile_config() {   # <name> <bench args...>
     local NAME=$1; shift
-    rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${NAME}_stats" -o "$TAG" -- python3 "$ROOT/bench.py" "$@" \
+    rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${NAME}_stats" -o "$TAG" -- python3 "$ROOT/bench.py" --full "$@" \
         > "$OUT/${NAME}_bench_under_rocprof.json" 2> "$OUT/${NAME}_rocprof_stats.err"
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/${NAME}_pmc_fetch" -o fetch -- python3 "$ROOT/bench.py" "$@" > /dev/null 2> "$OUT/${NAME}_rocprof_fetch.err"
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/${NAME}_pmc_write" -o write -- python3 "$ROOT/bench.py" "$@" > /dev/null 2> "$OUT/${NAME}_rocprof_write.err"
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/${NAME}_pmc_fetch" -o fetch -- python3 "$ROOT/bench.py" --full "$@" > /dev/null 2> "$OUT/${NAME}_rocprof_fetch.err"
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/${NAME}_pmc_write" -o write -- python3 "$ROOT/bench.py" --full "$@" > /dev/null 2> "$OUT/${NAME}_rocprof_write.err"
     local S=$(find "$OUT/${NAME}_stats" -name "*kernel_stats.csv" | head -1)
     local F=$(find "$OUT/${NAME}_pmc_fetch" -name "*counter_collection.csv" | head -1)
     local W=$(find "$OUT/${NAME}_pmc_write" -name "*counter_collection.csv" | head -1)
