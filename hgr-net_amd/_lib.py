@@ -79,6 +79,7 @@ SIGNATURES = {
     "hgr_gemm_nt_splitk": [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p],
     "hgr_gemm_tn_splitk": [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p],
     "hgr_gemm_tn_tile": [_i, _i],
+    "hgr_gemm_plan_capture": [_p, _i],
     "hgr_conv3x3_wgrad_splitk": [_p, _l, _p, _p, _l, _i, _i, _i, _i, _i, _i, _i, _p],
     "hgr_relu_bwd16": [_p, _p, _p, _l, _i, _p],
     "hgr_add16": [_p, _p, _p, _l, _i, _p],
@@ -114,6 +115,12 @@ SIGNATURES = {
 }
 
 
+class GemmLaunch(C.Structure):
+    """hgr_gemm_launch of include/hgr.h: one launch as hgr_gemm_plan_capture records it."""
+    _fields_ = [(name, C.c_int32) for name in ("kernel", "variant", "epilogue", "out_f32", "act", "grid_x", "grid_y", "tiles_m", "tiles_n", "total",
+                                                "nbig", "big_panels", "tiles_m_half", "group", "m_fastest", "vec_ok", "row0", "rows")]
+
+
 class HgrError(RuntimeError):
     pass
 
@@ -121,7 +128,7 @@ class HgrError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 4          # HGR_ABI_VERSION of include/hgr.h this wrapper was written against
+ABI_VERSION = 5          # HGR_ABI_VERSION of include/hgr.h this wrapper was written against
 
 
 def load() -> C.CDLL:

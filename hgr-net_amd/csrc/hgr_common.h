@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "../../include/hgr.h"
 
@@ -216,3 +217,25 @@ int hgr_set_error(int code, const char *fmt, ...);
     } while (0)
 
 static inline bool hgr_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+// Compute units of the current device, queried once; 256 (one MI355X) without a device (hgr_core.hip)
+int hgr_cu_count();
+
+// One development knob: the environment variable `env` (atoi; atof for a double knob) gives the initial value, `def` when it is not
+// set, `clamp` (optional) normalises what the environment said; the first get() reads it, a set() wins over the environment from then
+// on and returns the previous value.  Process-wide and unsynchronised, like the setters of hgr.h that sit on top of it.
+template <typename T = int> struct HgrKnob {
+    const char *env; T def; T (*clamp)(T) = nullptr;
+    bool known = false; T v = T();
+    T get() {
+        if (!known) {
+            const char *e = getenv(env);
+            v = !e ? def : std::is_floating_point<T>::value ? (T)atof(e) : (T)atoi(e);
+            if (clamp) v = clamp(v);
+            known = true;
+        }
+        return v;
+    }
+    T set(T nv) { const T prev = get(); v = nv; return prev; }
+};
+static inline int hgr_knob_bool(int v) { return v != 0; }

@@ -1,4 +1,7 @@
-// Host entry points of the NT GEMM family: argument validation, tile-plan choice, launch (kernels: hgr_gemm_128 / _256 / _duo .hip).
+// Host entry points of the NT GEMM family (kernels: hgr_gemm_128 / _256 / _duo / _ws / _p8 .hip, hgr_conv_direct.hip).  Every entry point is
+// validate -> plan -> launch: the plan functions below are plain host code that decide kernel, tile plan and grid (GemmLaunch) and launch
+// nothing; gemm_run() hands a plan to the launchers, which only select a template instantiation - or, when hgr_gemm_plan_capture armed
+// the calling thread, writes it out instead (tests/golden/gemm_plans.json pins the plan of every route on a machine without a GPU).
 #include "hgr_gemm_common.h"
 
 using namespace hgr_gemm;
@@ -9,24 +12,55 @@ int hgr_conv3x3_c32_launch(const void *x, const void *w, const float *bias, void
 namespace {
 constexpr int BM = 128, BN = 128;
 
-// development knobs of gemm_nt_duo, read once: HGR_GEMM_GROUP (raster group; default by shape, duo_group_for), HGR_GEMM_DBG (bit 8: sc1 output stores)
-int duo_group_env() {
-    static int g = -1;
-    if (g < 0) { const char *e = getenv("HGR_GEMM_GROUP"); g = e ? atoi(e) : 0; if (g < 0) g = 0; }
-    return g;
-}
-int duo_group() { return duo_group_env() ? duo_group_env() : 4; }          // gemm_nt_ws (no plan)
-// Row panels per raster group of a gemm_nt_duo launch (duo_apply_plan).  By shape unless HGR_GEMM_GROUP=n forces n: 4 (64 tiles in flight per
+// ---- development knobs (HgrKnob, hgr_common.h: the environment gives the initial value, the hgr_gemm_set_* setters win from then on) ----
+HgrKnob<> k_group{"HGR_GEMM_GROUP", 0, [](int v) { return v < 0 ? 0 : v; }};      // raster group of gemm_nt_duo / _ws; 0 = by shape (duo_group_for)
+HgrKnob<> k_tail{"HGR_DUO_TAIL", 1}, k_pb{"HGR_DUO_PB", -1};                       // hgr_gemm_set_tail: tail plan on / off, forced full panels
+HgrKnob<double> k_half_cost{"HGR_DUO_HALF_COST", 0.55, [](double v) { return v > 0.1 ? v : 0.55; }};
+HgrKnob<> k_tile{"HGR_GEMM_TILE", 0};                                              // hgr_gemm_set_tile: 0 | 128 | 256 | 2
+HgrKnob<> k_split{"HGR_GEMM_SPLIT", 1};                                            // the two-launch split plan of hgr_gemm_nt
+HgrKnob<> k_conv_direct{"HGR_CONV_DIRECT", 1}, k_conv_duo{"HGR_CONV_DUO", 1};      // 0 keeps the implicit GEMM / the 128 and 256 kernels
+// Persistent form of the residual producers.  Default: at most two workgroups per CU, each walking its share of the tiles (see gemm_nt_duo);
+// HGR_DUO_PERSIST=0 = one workgroup per tile (A/B runs).  Measured on the ViT-B/32 evaluation step, interleaved pairs on one box: every
+// launch persistent 5.064 -> 5.008 ms (-1.1 %; by shape proj 128.6 -> 123.5 us, out 50.1 -> 48.5, fc unchanged), the producers only
+// 5.137 -> 5.104 (-0.6 %).  Bit-identical.
+HgrKnob<> k_persist{"HGR_DUO_PERSIST", 1, hgr_knob_bool};                          // hgr_gemm_set_persist
+// gemm_nt_ws, default OFF: measured equal to or slower than gemm_nt_duo on every tower shape (profiles/NOTES.md, round 5) - the epilogue's
+// vector instructions cost their SIMD's matrix wave the same issue slots whichever wave executes them, and LDS bandwidth bounds both
+HgrKnob<> k_ws{"HGR_WS", 0, hgr_knob_bool};                                        // hgr_gemm_set_ws
+HgrKnob<> k_p8{"HGR_P8", 2, [](int v) { return v >= 0 && v <= 2 ? v : 2; }};       // hgr_gemm_set_p8: 0 never, 1 wherever p8_covers, 2 by shape (p8_wanted)
+
+int duo_group() { return k_group.get() ? k_group.get() : 4; }          // gemm_nt_ws, and m-fastest rasters of gemm_nt_duo
+// Row panels per raster group of a gemm_nt_duo launch (plan_duo).  By shape unless HGR_GEMM_GROUP=n forces n: 4 (64 tiles in flight per
 // XCD = 4 row panels x 16 column panels), but ONE for launches of at most 8 column panels - the few tiles that share an activation
 // panel are then dispatched back to back instead of 4 slots apart.  Measured (tools/raster_split_ab.sh, FETCH_SIZE per launch, ViT-B/32
 // step): the N = 768 producers 250 -> 222 MB (group 2: 232, 8: 280), patch GEMM 345 -> < 300; c_fc (24 column panels) 207 MB at 4,
 // 241 / 270 at 2 / 1, 219 at 8.  Step times of all three BASELINE configurations unchanged (tools/group_ab.sh: 4.953 vs 4.949 ms,
 // 10.08 vs 10.09 ms, 224.1 vs 224.8 ms): this trims fabric traffic, not time.
-int duo_group_for(int tiles_n) { return duo_group_env() ? duo_group_env() : (tiles_n <= 8 ? 1 : 4); }
+int duo_group_for(int tiles_n) { return k_group.get() ? k_group.get() : (tiles_n <= 8 ? 1 : 4); }
 int duo_dbg() {
-    static int d = -1;
-    if (d < 0) d = hgr_lab_env("HGR_GEMM_DBG");          // lab builds only (hgr_common.h): 0 in libhgr.so
+    static const int d = hgr_lab_env("HGR_GEMM_DBG");    // lab builds only (hgr_common.h): 0 in libhgr.so; bit 8: sc1 output stores
     return d;
+}
+
+// One launch as the plan step decides it: which kernel and instantiation, the grid, the plan fields of GemmArgs and the rows of the
+// call it covers (hgr_gemm_nt's split plan makes two launches over disjoint row ranges)
+struct GemmLaunch {
+    int kernel = 0;               // HGR_KERNEL_* (hgr.h); 0 = no launch
+    int variant = 0;              // V128_* | conv of gemm_nt_256 | ln form of gemm_nt_duo | WS_* | input channels of the direct convolution
+    int epilogue = HGR_EPI_NONE; bool out32 = false;
+    int act = 0;                  // gemm_nt_ws / gemm_nt_p8: 0 none, 1 QuickGELU, 2 ReLU
+    unsigned grid_x = 0, grid_y = 1;
+    int tiles_m = 0, tiles_n = 0, total = 0, nbig = 0, big_panels = 0, tiles_m_half = 0, group = 0;      // -> GemmArgs
+    int row0 = 0, rows = 0;
+};
+
+// gemm_nt_128 / gemm_nt_256 on TM x TN tiles, one per workgroup
+GemmLaunch plan_tiles(int kernel, int variant, int epi, bool out32, int M, int N, int TM, int TN, unsigned grid_y = 1) {
+    GemmLaunch L;
+    L.kernel = kernel; L.variant = variant; L.epilogue = epi; L.out32 = out32; L.rows = M;
+    L.tiles_m = (M + TM - 1) / TM; L.tiles_n = (N + TN - 1) / TN;
+    L.grid_x = (unsigned)(L.tiles_m * L.tiles_n); L.grid_y = grid_y;
+    return L;
 }
 
 // Tail plan of gemm_nt_duo.  The chip runs 512 of its workgroups at a time (2 per CU); a launch of T > 512 full tiles that is not
@@ -36,18 +70,13 @@ int duo_dbg() {
 // list-scheduling the two tile kinds on 512 slots (a half tile priced at HGR_DUO_HALF_COST = 0.55 of a full one: half the MFMAs, the
 // same per-tile overhead) over the candidate panel counts; HGR_DUO_TAIL=0 switches it off, HGR_DUO_PB=n forces n full panels.
 struct DuoPlan { int big_panels, nbig, tiles_m_half, grid; };
-int tail_env = -2, pb_env = -2;              // hgr_gemm_set_tail / HGR_DUO_TAIL, HGR_DUO_PB
-double half_cost = 0.55;
-DuoPlan duo_plan(int M, int N, bool allow_tail) {
-    if (tail_env == -2) {
-        const char *e = getenv("HGR_DUO_TAIL"); tail_env = e ? atoi(e) : 1;
-        const char *f = getenv("HGR_DUO_PB"); pb_env = f ? atoi(f) : -1;
-        const char *h = getenv("HGR_DUO_HALF_COST"); if (h && atof(h) > 0.1) half_cost = atof(h);
-    }
+DuoPlan duo_plan(int M, int N) {
+    const int tail = k_tail.get(), pb_forced = k_pb.get();
+    const double half_cost = k_half_cost.get();
     const int tiles_m = (M + 255) / 256, tiles_n = (N + 127) / 128, S = 512;
     const int64_t T = (int64_t)tiles_m * tiles_n;
     DuoPlan best{tiles_m, (int)T, 0, (int)T};
-    if (allow_tail && tail_env && pb_env < 0 && M > 128 && (T <= S / 4 || (tiles_m <= 2 && T <= S))) {
+    if (tail && pb_forced < 0 && M > 128 && (T <= S / 4 || (tiles_m <= 2 && T <= S))) {
         // a launch that covers a fraction of the chip (the class-token GEMMs of a ViT's last block: 512 rows) is bound by what ONE
         // workgroup can pull per K-tile, not by the matrix cores: all half tiles = twice the workgroups, 2/3 of the bytes per K-tile each.
         // Likewise at most two row panels on fewer tiles than slots (the class-logits GEMM and hgr_logits_eval at batch 512: 356
@@ -55,11 +84,11 @@ DuoPlan duo_plan(int M, int N, bool allow_tail) {
         best.big_panels = 0; best.nbig = 0; best.tiles_m_half = (M + 127) / 128; best.grid = best.tiles_m_half * tiles_n;
         return best;
     }
-    if (!allow_tail || !tail_env || T <= S || T % S == 0) return best;
+    if (!tail || T <= S || T % S == 0) return best;
     // measured (tools/tail_sweep.py, ViT-B/32 tower launches at batch 512, cold operands): last round 15 - 17 % full (out, proj, patch:
     // 600 / 588 tiles) -13 %, -14.5 %, -11 %; last round 52 % full (qkv, 1800 tiles) +-0; 69 % full (fc, 2400 tiles) +2 %: a
     // half-full last round already overlaps well, and half tiles stage fewer flops per byte
-    if (pb_env < 0 && (T % S) * 100 > 45 * (int64_t)S) return best;
+    if (pb_forced < 0 && (T % S) * 100 > 45 * (int64_t)S) return best;
     auto makespan = [&](int pb) {
         const int64_t nb = (int64_t)pb * tiles_n;
         const int mh = M - pb * 256;
@@ -81,7 +110,7 @@ DuoPlan duo_plan(int M, int N, bool allow_tail) {
     };
     int pick = tiles_m;
     double bm = makespan(tiles_m);
-    if (pb_env >= 0) pick = pb_env < tiles_m ? pb_env : tiles_m;
+    if (pb_forced >= 0) pick = pb_forced < tiles_m ? pb_forced : tiles_m;
     else
         for (int pb = tiles_m - 1; pb >= 0 && pb >= tiles_m - 96; --pb) {
             const double m = makespan(pb);
@@ -96,57 +125,208 @@ DuoPlan duo_plan(int M, int N, bool allow_tail) {
     best.grid = best.nbig + best.tiles_m_half * tiles_n;
     return best;
 }
-void duo_apply_plan(GemmArgs &a, bool allow_tail, dim3 &grid) {
-    const DuoPlan pl = duo_plan(a.M, a.N, allow_tail);
-    a.nbig = pl.nbig; a.big_panels = pl.big_panels; a.tiles_m_half = pl.tiles_m_half;
-    a.group = a.m_fastest ? duo_group() : duo_group_for((a.N + 127) / 128);
+
+// gemm_nt_duo: 256 x 128 tiles with the tail plan, raster group by shape; ln = the form (launch_duo)
+GemmLaunch plan_duo(const GemmArgs &a, int ln, int epi, bool out32) {
+    GemmLaunch L;
+    L.kernel = HGR_KERNEL_DUO; L.variant = ln; L.epilogue = epi; L.out32 = out32; L.rows = a.M;
+    L.tiles_m = (a.M + 255) / 256; L.tiles_n = (a.N + 127) / 128;
+    const DuoPlan pl = duo_plan(a.M, a.N);
+    L.nbig = pl.nbig; L.big_panels = pl.big_panels; L.tiles_m_half = pl.tiles_m_half;
+    L.group = a.m_fastest ? duo_group() : duo_group_for(L.tiles_n);
     if (duo_dbg() & 64) fprintf(stderr, "[duo_plan] M=%d N=%d K=%d -> %d full panels (%d tiles) + %d half panels, grid %d\n",
                                      a.M, a.N, a.K, pl.big_panels, pl.nbig, pl.tiles_m_half, pl.grid);
-    grid = dim3((unsigned)pl.grid);
+    L.grid_x = (unsigned)pl.grid;
+    // The persistent form (k_persist) for the residual producers (ln == 1, the only instantiations compiled with the tile loop) on launches
+    // of up to two rounds of the chip's slots - the launches that gain (their epilogue's read-modify-write drains beside the next tile's
+    // first operand loads).  Launches of many rounds LOSE with the static deal (ViT-L/14 training step 221.2 -> 223.6 ms, RN50 step
+    // 9.58 -> 9.66 ms with every launch persistent): the dispatcher's first-free-slot order balances the slots' drifting speeds, the
+    // fixed stride does not; the consumer / plain launches of one to two rounds measured neutral to slightly negative (RN50 9.97 -> 10.03 ms).
+    int slots = 2 * hgr_cu_count() & ~7;         // whole multiples of the 8 XCDs: virtual block v and physical block v % grid sit on the same XCD
+    if (slots < 8) slots = 8;
+    if (k_persist.get() && ln == 1 && pl.grid > slots && pl.grid <= 2 * slots) { L.total = pl.grid; L.grid_x = (unsigned)slots; }
+    return L;
 }
 
-// tile plan override (hgr_gemm_set_tile); HGR_GEMM_TILE=128|256|2 sets the initial value
-int g_force_tile = -1;
-int hgr_gemm_force_tile() {
-    if (g_force_tile < 0) { const char *e = getenv("HGR_GEMM_TILE"); g_force_tile = e ? atoi(e) : 0; }
-    return g_force_tile;
+// gemm_nt_ws: whole 256 x 128 tiles (ws_covers), one persistent workgroup per CU walks them
+GemmLaunch plan_ws(int M, int N, int mode, int epi, int act) {
+    GemmLaunch L;
+    L.kernel = HGR_KERNEL_WS; L.variant = mode; L.epilogue = epi; L.out32 = mode == WS_LNP; L.act = act; L.rows = M;
+    L.tiles_m = M / 256; L.tiles_n = N / 128; L.total = L.tiles_m * L.tiles_n; L.group = duo_group();
+    L.grid_x = (unsigned)(ws_cus() < L.total ? ws_cus() : L.total);
+    return L;
+}
+
+// gemm_nt_p8: whole 256 x 256 tiles (p8_covers), one persistent workgroup per CU walks them
+GemmLaunch plan_p8(int M, int N, int act) {
+    GemmLaunch L;
+    L.kernel = HGR_KERNEL_P8; L.epilogue = act ? HGR_EPI_BIAS_QUICKGELU : HGR_EPI_BIAS; L.act = act; L.rows = M;
+    L.tiles_m = M / 256; L.tiles_n = N / 256; L.group = duo_group();
+    const int tiles = L.tiles_m * L.tiles_n;
+    L.grid_x = (unsigned)(tiles < hgr_cu_count() ? tiles : hgr_cu_count());
+    return L;
+}
+
+// By shape: measured against gemm_nt_duo (tools/p8_bench.py, back to back, one MI355X, bit-identical): 25 600 x 3 072 x 3 072
+// 436 -> 394 us (1 108 -> 1 228 TF/s), ViT-L/14's c_fc 65 536 x 4 096 x 1 024 543 -> 519, ViT-B/32's c_fc (K = 768, 4.7 tiles per CU)
+// 128.0 -> 126.2 back to back and 132.5 -> 131.8 in the step (the step itself unchanged), its k / v projection (2.3 tiles per CU)
+// 70.9 -> 74.3: a K-tile of this form takes ~3 400 clocks where fill, matrix and LDS time are ~2 000 each (ablation builds at
+// K = 3 072: 390 us; no fragment reads 378; no LDS-DMA behind the prologue 318; neither 274 - the fill that does not overlap is
+// added), and a tile's prologue and epilogue run beside nothing - so it pays with long K and many tiles per CU only.
+bool p8_wanted(int M, int N, int K) {
+    const int m = k_p8.get();
+    if (!m || !p8_covers(M, N, K)) return false;
+    return m == 1 || (K >= 1024 && (int64_t)(M / 256) * (N / 256) >= 4 * hgr_cu_count());
+}
+
+// ---- plan capture (hgr_gemm_plan_capture) and the launch step -----------------------------------------------------------
+thread_local hgr_gemm_launch *cap_out = nullptr;
+thread_local int cap_max = 0;
+// every covered entry point holds one: whichever way the call ends (planned or rejected), the calling thread is disarmed
+struct CaptureScope { ~CaptureScope() { cap_out = nullptr; cap_max = 0; } };
+
+// rows [row0, row0 + rows) of the call `a` describes (csz / rsz: element sizes of C and of the second operand)
+GemmArgs gemm_rows(GemmArgs a, int row0, int rows, size_t csz, size_t rsz) {
+    a.A += (size_t)row0 * a.lda * 2;
+    a.C = (char *)a.C + (size_t)row0 * a.ldc * csz;
+    if (a.res) a.res = (const float *)((const char *)a.res + (size_t)row0 * a.ldr * rsz);
+    a.M = rows; a.m_fastest = gemm_m_fastest(rows, a.N, a.K);
+    return a;
+}
+
+int gemm_run(const char *who, const GemmArgs &call, const GemmLaunch *plan, int n, int dtype, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    HGR_REQUIRE(!cap_out || n <= cap_max, "%s: %d launches, hgr_gemm_plan_capture armed for %d", who, n, cap_max);
+    for (int i = 0; i < n; ++i) {
+        const GemmLaunch &L = plan[i];
+        GemmArgs a = L.rows == call.M ? call : gemm_rows(call, L.row0, L.rows, L.out32 ? 4 : 2, epi_has_idn16(L.epilogue) ? 2 : 4);
+        a.tiles_m = L.tiles_m; a.tiles_n = L.tiles_n; a.total = L.total;
+        a.nbig = L.nbig; a.big_panels = L.big_panels; a.tiles_m_half = L.tiles_m_half; a.group = L.group;
+        if (cap_out) {
+            cap_out[i] = hgr_gemm_launch{L.kernel, L.variant, L.epilogue, L.out32, L.act, (int32_t)L.grid_x, (int32_t)L.grid_y, a.tiles_m, a.tiles_n, a.total,
+                                         a.nbig, a.big_panels, a.tiles_m_half, a.group, a.m_fastest, a.vec_ok, L.row0, L.rows};
+            continue;
+        }
+        const dim3 grid(L.grid_x, L.grid_y);
+        switch (L.kernel) {
+            case HGR_KERNEL_128: launch_128(a, dtype, L.epilogue, L.out32, L.variant, grid, s); break;
+            case HGR_KERNEL_256: launch_256(a, dtype, L.epilogue, L.out32, L.variant != 0, grid, s); break;
+            case HGR_KERNEL_DUO: launch_duo(a, dtype, L.epilogue, L.out32, L.variant, grid, s); break;
+            case HGR_KERNEL_WS: launch_ws(a, dtype, L.variant, L.act, L.variant != WS_LNC && epi_has_bias(L.epilogue), grid, s); break;   // hasb selects among the WS_PLAIN instantiations only
+            default: launch_p8(a, dtype, L.act, grid, s); break;
+        }
+    }
+    if (cap_out) return HGR_OK;
+    HGR_CHECK_LAUNCH(who);
+    return HGR_OK;
 }
 
 }  // namespace
 
+extern "C" int hgr_gemm_plan_capture(hgr_gemm_launch *out, int max_launches) {
+    if (!out && max_launches == 0) {             // disarm; 1 = no covered call had consumed the capture
+        const int armed = cap_out != nullptr;
+        CaptureScope disarm;
+        return armed;
+    }
+    HGR_REQUIRE(out && max_launches >= 1, "hgr_gemm_plan_capture: out must not be null and max_launches >= 1 (or NULL, 0 to disarm), got %d", max_launches);
+    cap_out = out; cap_max = max_launches;
+    return HGR_OK;
+}
+
 extern "C" int hgr_gemm_set_tail(int enabled, int full_panels) {
     HGR_REQUIRE((enabled == 0 || enabled == 1) && full_panels >= -1, "hgr_gemm_set_tail: enabled must be 0 or 1, full_panels >= -1 (-1 = choose), got %d, %d", enabled, full_panels);
-    duo_plan(1, 1, false);                       // reads the environment once, so that it cannot overwrite this call later
-    const int prev = tail_env;
-    tail_env = enabled; pb_env = full_panels;
-    return prev;
+    k_pb.set(full_panels);
+    return k_tail.set(enabled);
 }
 
 extern "C" int hgr_gemm_set_tile(int tile) {
     HGR_REQUIRE(tile == 0 || tile == 128 || tile == 256 || tile == 2, "hgr_gemm_set_tile: tile must be 0, 128, 256 or 2 (256 x 128 tiles, two workgroups per CU), got %d", tile);
-    const int prev = hgr_gemm_force_tile();
-    g_force_tile = tile;
-    return prev;
+    return k_tile.set(tile);
 }
 
 extern "C" int hgr_gemm_set_ws(int enabled) {
     HGR_REQUIRE(enabled == 0 || enabled == 1, "hgr_gemm_set_ws: enabled must be 0 or 1, got %d", enabled);
-    return ws_set(enabled);
+    return k_ws.set(enabled);
 }
 
 extern "C" int hgr_gemm_set_p8(int mode) {
     HGR_REQUIRE(mode >= 0 && mode <= 2, "hgr_gemm_set_p8: mode must be 0 (never), 1 (wherever it covers) or 2 (by shape), got %d", mode);
-    return p8_set(mode);
+    return k_p8.set(mode);
 }
 
 extern "C" int hgr_gemm_set_persist(int enabled) {
     HGR_REQUIRE(enabled == 0 || enabled == 1, "hgr_gemm_set_persist: enabled must be 0 or 1, got %d", enabled);
-    return duo_set_persist(enabled);
+    return k_persist.set(enabled);
 }
+
+// ---- hgr_gemm_nt ---------------------------------------------------------------------------------------------------------
+namespace {
+// Kernel and tile plan of one hgr_gemm_nt call (validated; `a` = the whole call): one launch, or two for the split plan.  Returns the count.
+int plan_gemm_nt(const GemmArgs &a, int epilogue, bool out_f32, bool ws_operands_ok, GemmLaunch plan[2]) {
+    const int M = a.M, N = a.N, K = a.K;
+    // rows [m_lo, m_lo + m_cnt) with one tile size
+    auto tiled = [&](int m_lo, int m_cnt, bool big) {
+        // outputs at most 64 wide (1x1 convolutions into the 64-channel ResNet stages): the 256 x 64 arrangement of the small kernel
+        const bool tall = !big && N <= 64 && m_cnt >= 1024 && epilogue == HGR_EPI_BIAS_RELU && !out_f32;
+        GemmLaunch L = tall  ? plan_tiles(HGR_KERNEL_128, V128_TALL, HGR_EPI_BIAS_RELU, false, m_cnt, 1, 256, 1)
+                       : big ? plan_tiles(HGR_KERNEL_256, 0, epilogue, out_f32, m_cnt, N, 256, 256)
+                             : plan_tiles(HGR_KERNEL_128, V128_PLAIN, epilogue, out_f32, m_cnt, N, BM, BN);
+        L.row0 = m_lo;
+        return L;
+    };
+    // Tile choice.  The 256^2 deep-pipelined kernel owns a CU (one 512-thread workgroup), so a launch runs in rounds of
+    // 256 workgroups; 128^2 tiles run 2 workgroups per CU.  Three plans are priced with measured tile times: all big,
+    // all small, or full rounds of big tiles on the first row panels + the remaining panels on the small-tile kernel in a
+    // second launch (pays off at long K, where a mostly empty last big round is expensive: c_proj / patch GEMM).
+    const int force = k_tile.get();
+    const int tn256 = (N + 255) / 256, tm256 = (M + 255) / 256;
+    const int64_t t256 = (int64_t)tm256 * tn256;
+    const int64_t t128 = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
+    // measured tile times on MI355X (us): 256^2 tile ~ 1.75 per K-tile + 14 (prologue + epilogue, nothing overlaps them
+    // at one workgroup per CU); 128^2 tile at 2 per CU ~ 1.08 per K-tile + 9
+    const double Tb = 1.75 * (K / 64) + 14.0, Ts = 1.08 * (K / 64) + 9.0;
+    const double cost_small = (double)((t128 + 511) / 512) * Ts;
+    const double cost_big = (double)((t256 + 255) / 256) * Tb;
+    const int64_t rounds = t256 / 256;
+    const int big_panels = (int)((rounds * 256) / tn256);
+    const int m1 = big_panels * 256;
+    double cost_split = 1e30;
+    if (k_split.get() && rounds >= 1 && m1 > 0 && m1 < M) {
+        const int64_t ts = (int64_t)((M - m1 + 127) / 128) * ((N + 127) / 128);
+        cost_split = (double)rounds * Tb + (double)((ts + 511) / 512) * Ts + 2.0;          // + one kernel boundary
+    }
+    // 256 x 128 tiles, two workgroups per CU (gemm_nt_duo): fp32 residual / 16-bit epilogues of the transformer towers
+    const bool duo_ok = K >= 128 && (out_f32 || (epilogue != HGR_EPI_BIAS_RESIDUAL && epilogue != HGR_EPI_ACCUM)) &&
+                        (int64_t)M * a.lda * 2 < (1ll << 32) && (int64_t)N * a.ldw * 2 < (1ll << 32) && a.ldc < (1 << 20) && a.ldr < (1 << 20);
+    // Plan choice for the shapes gemm_nt_duo covers: measured (tools/gemm_plan_ab.py, same-process A/B, f16, one MI355X; bit-identical
+    // outputs): qkv 97 -> 91 us, out-proj 59 -> 49, c_fc 136 -> 124, c_proj 145 -> 126, patch 124 -> 118, class logits 24.7 -> 20.7,
+    // text qkv 168 -> 154, ViT-L/14 out / proj 411 -> 361 / 1029 -> 999, ViT-L/14 qkv / fc a tie; a launch with fewer tiles than
+    // half the chip's 512 slots (small text batches, ragged test shapes) stays on the 128^2 / cost-model plans.
+    const int64_t tduo = (int64_t)((M + 255) / 256) * ((N + 127) / 128);
+    // ... and an output much narrower than its 128-column tiles (the 64-channel ResNet stage: half of every tile would be padding;
+    // measured 252 vs 194 us on the 256 x 64 arrangement of the small kernel) stays where it was
+    const bool duo_fits = (N + 127) / 128 * 128 - N <= N / 8;
+    // the role-split kernel (gemm_nt_ws: the epilogue runs in helper waves under the next tile's MFMAs) for 16-bit outputs made of whole tiles
+    // (not BIAS_QUICKGELU: in gemm_nt_duo's plain f16 instantiation hipcc fuses the last product of QuickGELU with the conversion -
+    // v_fma_mixlo_f16, ONE rounding - and does not in the row-layout epilogue; the folded-LayerNorm form, the one the towers use, matches)
+    const bool ws_epi = epilogue == HGR_EPI_NONE || epilogue == HGR_EPI_BIAS || epilogue == HGR_EPI_BIAS_RELU;
+    if (duo_ok && force == 0 && k_ws.get() && !out_f32 && ws_epi && ws_operands_ok && ws_covers(M, N, K, WS_PLAIN))
+        plan[0] = plan_ws(M, N, WS_PLAIN, epilogue, epilogue == HGR_EPI_BIAS_RELU ? 2 : 0);
+    else if (duo_ok && (force == 2 || (force == 0 && tduo >= 256 && duo_fits))) plan[0] = plan_duo(a, 0, epilogue, out_f32);
+    else if (force == 128 || K < 128) plan[0] = tiled(0, M, false);
+    else if (epi_has_idn16(epilogue) && force != 256) plan[0] = tiled(0, M, false);   // only the 128 kernel loads the identity / stores by full lines
+    else if (force == 256) plan[0] = tiled(0, M, true);
+    else if (cost_split < cost_big && cost_split < cost_small) { plan[0] = tiled(0, m1, true); plan[1] = tiled(m1, M - m1, false); return 2; }
+    else plan[0] = tiled(0, M, cost_big <= cost_small && t256 >= 128);
+    return 1;
+}
+}  // namespace
 
 extern "C" int hgr_gemm_nt(const void *A, int64_t lda, const void *W, int64_t ldw, void *C, int64_t ldc,
                            const float *bias, const void *residual, int64_t ldr,
                            int M, int N, int K, int dtype, int epilogue, int out_f32, void *stream) {
+    CaptureScope capture;
     HGR_REQUIRE(A && W && C, "hgr_gemm_nt: null operand");
     HGR_REQUIRE(M >= 1 && N >= 1 && K >= BK, "hgr_gemm_nt: bad shape M=%d N=%d K=%d", M, N, K);
     HGR_REQUIRE(K % BK == 0, "hgr_gemm_nt: K=%d must be a multiple of %d (pad the operands)", K, BK);
@@ -165,170 +345,75 @@ extern "C" int hgr_gemm_nt(const void *A, int64_t lda, const void *W, int64_t ld
     if (epi_has_bias(epilogue)) vec = vec && hgr_aligned(bias, 16);
     if (epilogue == HGR_EPI_BIAS_RESIDUAL) vec = vec && (ldr % 4 == 0) && hgr_aligned(residual, 16);
     if (epi_has_idn16(epilogue)) vec = vec && (ldr % 4 == 0) && hgr_aligned(residual, 8);
-    static int dbg = -1, split_env = -1;
-    if (dbg < 0) dbg = hgr_lab_env("HGR_GEMM_DBG");
-    if (split_env < 0) { const char *e = getenv("HGR_GEMM_SPLIT"); split_env = e ? atoi(e) : 1; }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t csz = out_f32 ? 4 : 2, rsz = epi_has_idn16(epilogue) ? 2 : 4;
-
-    // launch rows [m_lo, m_lo + m_cnt) with one tile size
-    auto launch = [&](int m_lo, int m_cnt, bool big) {
-        GemmArgs a;
-        a.A = (const char *)A + (size_t)m_lo * lda * 2; a.lda = lda; a.W = (const char *)W; a.ldw = ldw;
-        a.C = (char *)C + (size_t)m_lo * ldc * csz; a.ldc = ldc; a.bias = bias;
-        a.res = residual ? (const float *)((const char *)residual + (size_t)m_lo * ldr * rsz) : nullptr; a.ldr = ldr;
-        a.M = m_cnt; a.N = N; a.K = K;
-        const int T = big ? 256 : 128;
-        a.tiles_m = (m_cnt + T - 1) / T;
-        a.tiles_n = (N + T - 1) / T;
-        // each XCD owns a contiguous range of tile ids; the operand indexed by the slow tile index is fetched ~once,
-        // the other one once per XCD.  Make the bigger operand the once-fetched one.
-        a.m_fastest = ((int64_t)N * K > (int64_t)m_cnt * K) ? 1 : 0;
-        a.vec_ok = vec ? 1 : 0;
-        a.dbg = dbg; a.kc = 0; a.csplit = 0;
-        // outputs at most 64 wide (1x1 convolutions into the 64-channel ResNet stages): the 256 x 64 arrangement of the small kernel
-        if (!big && N <= 64 && m_cnt >= 1024 && epilogue == HGR_EPI_BIAS_RELU && !out_f32) {
-            a.tiles_m = (m_cnt + 255) / 256; a.tiles_n = 1;
-            launch_128(a, dtype, HGR_EPI_BIAS_RELU, false, V128_TALL, dim3((unsigned)a.tiles_m), s);
-            return;
-        }
-        dim3 grid((unsigned)(a.tiles_m * a.tiles_n));
-        if (big) launch_256(a, dtype, epilogue, out_f32 != 0, false, grid, s);
-        else launch_128(a, dtype, epilogue, out_f32 != 0, V128_PLAIN, grid, s);
-    };
-
-    // Tile choice.  The 256^2 deep-pipelined kernel owns a CU (one 512-thread workgroup), so a launch runs in rounds of
-    // 256 workgroups; 128^2 tiles run 2 workgroups per CU.  Three plans are priced with measured tile times: all big,
-    // all small, or full rounds of big tiles on the first row panels + the remaining panels on the small-tile kernel in a
-    // second launch (pays off at long K, where a mostly empty last big round is expensive: c_proj / patch GEMM).
-    const int force = hgr_gemm_force_tile();
-    const int tn256 = (N + 255) / 256, tm256 = (M + 255) / 256;
-    const int64_t t256 = (int64_t)tm256 * tn256;
-    const int64_t t128 = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
-    // measured tile times on MI355X (us): 256^2 tile ~ 1.75 per K-tile + 14 (prologue + epilogue, nothing overlaps them
-    // at one workgroup per CU); 128^2 tile at 2 per CU ~ 1.08 per K-tile + 9
-    const double Tb = 1.75 * (K / 64) + 14.0, Ts = 1.08 * (K / 64) + 9.0;
-    const double cost_small = (double)((t128 + 511) / 512) * Ts;
-    const double cost_big = (double)((t256 + 255) / 256) * Tb;
-    const int64_t rounds = t256 / 256;
-    const int big_panels = (int)((rounds * 256) / tn256);
-    const int m1 = big_panels * 256;
-    double cost_split = 1e30;
-    if (split_env && rounds >= 1 && m1 > 0 && m1 < M) {
-        const int64_t ts = (int64_t)((M - m1 + 127) / 128) * ((N + 127) / 128);
-        cost_split = (double)rounds * Tb + (double)((ts + 511) / 512) * Ts + 2.0;          // + one kernel boundary
-    }
-    // 256 x 128 tiles, two workgroups per CU (gemm_nt_duo): fp32 residual / 16-bit epilogues of the transformer towers
-    const bool duo_ok = K >= 128 && (out_f32 || (epilogue != HGR_EPI_BIAS_RESIDUAL && epilogue != HGR_EPI_ACCUM)) &&
-                        (int64_t)M * lda * 2 < (1ll << 32) && (int64_t)N * ldw * 2 < (1ll << 32) && ldc < (1 << 20) && ldr < (1 << 20);
-    auto launch_d = [&]() {
-        GemmArgs a;
-        a.A = (const char *)A; a.lda = lda; a.W = (const char *)W; a.ldw = ldw; a.C = C; a.ldc = ldc; a.bias = bias;
-        a.res = (const float *)residual; a.ldr = ldr; a.M = M; a.N = N; a.K = K;
-        a.tiles_m = (M + 255) / 256; a.tiles_n = (N + 127) / 128;
-        a.m_fastest = ((int64_t)N * K > (int64_t)M * K) ? 1 : 0;
-        a.vec_ok = vec ? 1 : 0; a.dbg = dbg; a.kc = 0; a.csplit = 0; a.group = duo_group();
-        dim3 grid;
-        duo_apply_plan(a, true, grid);
-        launch_duo(a, dtype, epilogue, out_f32 != 0, 0, grid, s);
-    };
-    // Plan choice for the shapes gemm_nt_duo covers: measured (tools/gemm_plan_ab.py, same-process A/B, f16, one MI355X; bit-identical
-    // outputs): qkv 97 -> 91 us, out-proj 59 -> 49, c_fc 136 -> 124, c_proj 145 -> 126, patch 124 -> 118, class logits 24.7 -> 20.7,
-    // text qkv 168 -> 154, ViT-L/14 out / proj 411 -> 361 / 1029 -> 999, ViT-L/14 qkv / fc a tie; a launch with fewer tiles than
-    // half the chip's 512 slots (small text batches, ragged test shapes) stays on the 128^2 / cost-model plans.
-    const int64_t tduo = (int64_t)((M + 255) / 256) * ((N + 127) / 128);
-    // ... and an output much narrower than its 128-column tiles (the 64-channel ResNet stage: half of every tile would be padding;
-    // measured 252 vs 194 us on the 256 x 64 arrangement of the small kernel) stays where it was
-    const bool duo_fits = (N + 127) / 128 * 128 - N <= N / 8;
-    // the role-split kernel (gemm_nt_ws: the epilogue runs in helper waves under the next tile's MFMAs) for 16-bit outputs made of whole tiles
-    // (not BIAS_QUICKGELU: in gemm_nt_duo's plain f16 instantiation hipcc fuses the last product of QuickGELU with the conversion -
-    // v_fma_mixlo_f16, ONE rounding - and does not in the row-layout epilogue; the folded-LayerNorm form, the one the towers use, matches)
-    const bool ws_epi = epilogue == HGR_EPI_NONE || epilogue == HGR_EPI_BIAS || epilogue == HGR_EPI_BIAS_RELU;
-    if (duo_ok && force == 0 && ws_enabled() && !out_f32 && ws_epi && ldc % 8 == 0 && ldc < (1 << 23) && hgr_aligned(C, 16) && (!bias || hgr_aligned(bias, 16)) &&
-        ws_covers(M, N, K, WS_PLAIN)) {
-        GemmArgs a;
-        a.A = (const char *)A; a.lda = lda; a.W = (const char *)W; a.ldw = ldw; a.C = C; a.ldc = ldc; a.bias = bias;
-        a.res = nullptr; a.ldr = 0; a.M = M; a.N = N; a.K = K;
-        a.m_fastest = ((int64_t)N * K > (int64_t)M * K) ? 1 : 0;
-        a.vec_ok = 1; a.dbg = dbg; a.kc = 0; a.csplit = 0; a.group = duo_group();
-        launch_ws(a, dtype, WS_PLAIN, epilogue == HGR_EPI_BIAS_RELU ? 2 : 0, epilogue != HGR_EPI_NONE, s);
-    }
-    else if (duo_ok && (force == 2 || (force == 0 && tduo >= 256 && duo_fits))) launch_d();
-    else if (force == 128 || K < 128) launch(0, M, false);
-    else if (epi_has_idn16(epilogue) && force != 256) launch(0, M, false);   // only the 128 kernel loads the identity / stores by full lines
-    else if (force == 256) launch(0, M, true);
-    else if (cost_split < cost_big && cost_split < cost_small) { launch(0, m1, true); launch(m1, M - m1, false); }
-    else launch(0, M, cost_big <= cost_small && t256 >= 128);
-    HGR_CHECK_LAUNCH("hgr_gemm_nt");
-    return HGR_OK;
+    GemmArgs a = gemm_args(A, lda, W, ldw, C, ldc, M, N, K, vec, duo_dbg());
+    a.bias = bias; a.res = (const float *)residual; a.ldr = ldr;
+    const bool ws_operands_ok = ldc % 8 == 0 && ldc < (1 << 23) && hgr_aligned(C, 16) && (!bias || hgr_aligned(bias, 16));
+    GemmLaunch plan[2];
+    const int n = plan_gemm_nt(a, epilogue, out_f32 != 0, ws_operands_ok, plan);
+    if (plan[0].kernel == HGR_KERNEL_WS) { a.res = nullptr; a.ldr = 0; a.vec_ok = 1; }     // its three epilogues have no second operand
+    return gemm_run("hgr_gemm_nt", a, plan, n, dtype, stream);
 }
 
-static int conv3x3_launch(const void *x, const void *w, const float *bias, void *out,
-                          int B, int H, int W, int C, int Cout, int stride, int Kp, int dtype, bool relu, void *stream) {
-    HGR_REQUIRE(x && w && out && (bias || !relu), "hgr_conv3x3_nhwc: null operand");
-    HGR_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cout >= 1 && (stride == 1 || stride == 2), "hgr_conv3x3_nhwc: bad geometry B=%d H=%d W=%d Cout=%d stride=%d", B, H, W, Cout, stride);
-    HGR_REQUIRE(C >= 8 && C % 8 == 0 && C <= 16384, "hgr_conv3x3_nhwc: C=%d must be a multiple of 8 in [8, 16384]", C);
-    HGR_REQUIRE(Kp >= 9 * C && Kp % BK == 0, "hgr_conv3x3_nhwc: Kp=%d must be >= 9*C and a multiple of %d", Kp, BK);
-    HGR_REQUIRE(hgr_aligned(x, 16) && hgr_aligned(w, 16) && hgr_aligned(out, 8) && (!bias || hgr_aligned(bias, 16)) && Cout % 4 == 0, "hgr_conv3x3_nhwc: misaligned operand / Cout %% 4 != 0");
-    HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_conv3x3_nhwc: bad dtype %d", dtype);
-    // 32 input channels (the stem at 112 x 112): the direct kernel of hgr_conv_direct.hip; HGR_CONV_DIRECT=0 keeps the implicit GEMM
-    static int direct_env = -1;
-    if (direct_env < 0) { const char *e = getenv("HGR_CONV_DIRECT"); direct_env = e ? atoi(e) : 1; }
-    if (direct_env && C == 32 && stride == 1 && (Cout == 32 || Cout == 64) && Kp >= 288 && hgr_aligned(out, 16))
-        return hgr_conv3x3_c32_launch(x, w, bias, out, B, H, W, Cout, Kp, dtype, relu ? 1 : 0, stream, 0, 32);
+// ---- 3 x 3 convolutions ----------------------------------------------------------------------------------------------------
+namespace {
+// Input channels of the direct kernel (hgr_conv_direct.hip) that takes a convolution, 0 = the implicit GEMM; HGR_CONV_DIRECT=0 keeps the latter
+int conv_direct_channels(int C, int Cout, int stride, int Kp, int64_t in_pixels, bool out16_aligned) {
+    if (!k_conv_direct.get() || stride != 1 || !out16_aligned) return 0;
+    // 32 input channels (the stem at 112 x 112)
+    if (C == 32 && (Cout == 32 || Cout == 64) && Kp >= 288) return 32;
     // 64 -> 64 channels (layer1 of the ModifiedResNets): the implicit GEMM pulls every input byte nine times through LDS-DMA at
     // ~28 GB/s per CU (258 us at 56 x 56, batch 512); the halo-tile kernel reads it 1.27 times
-    if (direct_env && C == 64 && Cout == 64 && stride == 1 && Kp >= 576 && hgr_aligned(out, 16) && (int64_t)B * H * W >= 4096)
-        return hgr_conv3x3_c32_launch(x, w, bias, out, B, H, W, Cout, Kp, dtype, relu ? 1 : 0, stream, 0, 64);
-    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-    const int64_t M64 = (int64_t)B * Ho * Wo;
-    HGR_REQUIRE(M64 < (1ll << 31), "hgr_conv3x3_nhwc: too many output pixels");
-    GemmArgs a;
-    a.A = (const char *)x; a.lda = 0; a.W = (const char *)w; a.ldw = Kp;
-    a.C = out; a.ldc = Cout; a.bias = bias; a.res = nullptr; a.ldr = 0;
-    a.M = (int)M64; a.N = Cout; a.K = Kp;
-    a.tiles_m = (a.M + BM - 1) / BM; a.tiles_n = (Cout + BN - 1) / BN;
-    a.m_fastest = 0; a.vec_ok = 1; a.dbg = 0; a.kc = 0; a.csplit = 0;
-    a.cH = H; a.cW = W; a.cC = C; a.cStride = stride; a.cHo = Ho; a.cWo = Wo;
-    a.cMagic = (unsigned)(((1ull << 32) + (unsigned)C - 1) / (unsigned)C);
-    a.cUni = (C % 64 == 0) ? 1 : 0;
+    if (C == 64 && Cout == 64 && Kp >= 576 && in_pixels >= 4096) return 64;
+    return 0;
+}
+
+// the ladder of the implicit-GEMM convolution (`a` carries the geometry)
+GemmLaunch plan_conv3x3(const GemmArgs &a, int64_t in_pixels, bool relu, bool out16_aligned) {
+    const int C = a.cC, Cout = a.N, Kp = a.K, stride = a.cStride, force = k_tile.get(), epi = relu ? HGR_EPI_BIAS_RELU : HGR_EPI_NONE;
     // big tiles when the output is at least 256 wide-ish and the launch has >= 160 of them (measured at batch 512: 14x14x256
     // 160 -> 142 us with 392 tiles, 7x7x512 160 -> 135 us with 196 tiles; K is 2304 / 4608 there, so one round is long)
     const int64_t t256 = (int64_t)((a.M + 255) / 256) * ((Cout + 255) / 256);
     // ... and 256-wide tiles do not waste more columns than 128-wide ones would (Cout = 128: half of every 256^2 tile would be
     // padding - measured 1066 vs 646 us at 56x56x128 and 285 vs 160 us at 28x28x128, batch 512)
     const int waste256 = (Cout + 255) / 256 * 256 - Cout, waste128 = (Cout + 127) / 128 * 128 - Cout;
-    const bool big = relu && hgr_gemm_force_tile() != 128 && Kp >= 128 && Cout >= 128 && (t256 >= 160 || hgr_gemm_force_tile() == 256) && waste256 <= waste128;
+    const bool big = relu && force != 128 && Kp >= 128 && Cout >= 128 && (t256 >= 160 || force == 256) && waste256 <= waste128;
     // 256 x 128 tiles, two workgroups per CU (gemm_nt_duo with the implicit-im2col loader): C % 64 == 0, stride 1, outputs that fill
     // 128-column tiles, operands addressable with 32-bit offsets; HGR_CONV_DUO=0 keeps the kernels above
-    static int conv_duo_env = -1;
-    if (conv_duo_env < 0) { const char *e = getenv("HGR_CONV_DUO"); conv_duo_env = e ? atoi(e) : 1; }
     const int64_t tduo = (int64_t)((a.M + 255) / 256) * ((Cout + 127) / 128);
-    if (conv_duo_env && relu && a.cUni && stride == 1 && Cout % 128 == 0 && Kp == 9 * C && tduo >= 256 && hgr_aligned(out, 16) &&
-        (int64_t)B * H * W * C * 2 < (1ll << 31) && (int64_t)Cout * Kp * 2 < (1ll << 32) && hgr_gemm_force_tile() == 0) {
-        a.tiles_m = (a.M + 255) / 256; a.tiles_n = Cout / 128; a.group = duo_group();
-        a.ln_stats = nullptr; a.ln_flag = nullptr;
-        dim3 grid;
-        duo_apply_plan(a, true, grid);
-        launch_duo(a, dtype, HGR_EPI_BIAS_RELU, false, 5, grid, (hipStream_t)stream);
-        HGR_CHECK_LAUNCH("hgr_conv3x3_nhwc");
-        return HGR_OK;
-    }
-    if (big) {
-        a.tiles_m = (a.M + 255) / 256; a.tiles_n = (Cout + 255) / 256;
-        launch_256(a, dtype, HGR_EPI_BIAS_RELU, false, true, dim3((unsigned)(a.tiles_m * a.tiles_n)), (hipStream_t)stream);
-    } else {
-        if (Cout <= 64 && a.M >= 1024) {              // tall 256 x 64 tiles: no MFMAs spent on columns that do not exist
-            a.tiles_m = (a.M + 255) / 256; a.tiles_n = 1;
-            launch_128(a, dtype, relu ? HGR_EPI_BIAS_RELU : HGR_EPI_NONE, false, V128_CONV_TALL, dim3((unsigned)a.tiles_m), (hipStream_t)stream);
-            HGR_CHECK_LAUNCH("hgr_conv3x3_nhwc");
-            return HGR_OK;
-        }
-        launch_128(a, dtype, relu ? HGR_EPI_BIAS_RELU : HGR_EPI_NONE, false, V128_CONV, dim3((unsigned)(a.tiles_m * a.tiles_n)), (hipStream_t)stream);
-    }
-    HGR_CHECK_LAUNCH("hgr_conv3x3_nhwc");
-    return HGR_OK;
+    if (k_conv_duo.get() && relu && a.cUni && stride == 1 && Cout % 128 == 0 && Kp == 9 * C && tduo >= 256 && out16_aligned &&
+        in_pixels * C * 2 < (1ll << 31) && (int64_t)Cout * Kp * 2 < (1ll << 32) && force == 0)
+        return plan_duo(a, 5, HGR_EPI_BIAS_RELU, false);
+    if (big) return plan_tiles(HGR_KERNEL_256, 1, HGR_EPI_BIAS_RELU, false, a.M, Cout, 256, 256);
+    // tall 256 x 64 tiles: no MFMAs spent on columns that do not exist
+    if (Cout <= 64 && a.M >= 1024) return plan_tiles(HGR_KERNEL_128, V128_CONV_TALL, epi, false, a.M, 1, 256, 1);
+    return plan_tiles(HGR_KERNEL_128, V128_CONV, epi, false, a.M, Cout, BM, BN);
 }
+
+int conv3x3_launch(const void *x, const void *w, const float *bias, void *out,
+                   int B, int H, int W, int C, int Cout, int stride, int Kp, int dtype, bool relu, void *stream) {
+    CaptureScope capture;
+    HGR_REQUIRE(x && w && out && (bias || !relu), "hgr_conv3x3_nhwc: null operand");
+    HGR_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cout >= 1 && (stride == 1 || stride == 2), "hgr_conv3x3_nhwc: bad geometry B=%d H=%d W=%d Cout=%d stride=%d", B, H, W, Cout, stride);
+    HGR_REQUIRE(C >= 8 && C % 8 == 0 && C <= 16384, "hgr_conv3x3_nhwc: C=%d must be a multiple of 8 in [8, 16384]", C);
+    HGR_REQUIRE(Kp >= 9 * C && Kp % BK == 0, "hgr_conv3x3_nhwc: Kp=%d must be >= 9*C and a multiple of %d", Kp, BK);
+    HGR_REQUIRE(hgr_aligned(x, 16) && hgr_aligned(w, 16) && hgr_aligned(out, 8) && (!bias || hgr_aligned(bias, 16)) && Cout % 4 == 0, "hgr_conv3x3_nhwc: misaligned operand / Cout %% 4 != 0");
+    HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_conv3x3_nhwc: bad dtype %d", dtype);
+    if (const int direct = conv_direct_channels(C, Cout, stride, Kp, (int64_t)B * H * W, hgr_aligned(out, 16))) {
+        if (cap_out) { *cap_out = hgr_gemm_launch{HGR_KERNEL_CONV_DIRECT, direct, relu ? HGR_EPI_BIAS_RELU : HGR_EPI_NONE, 0, relu}; return HGR_OK; }
+        return hgr_conv3x3_c32_launch(x, w, bias, out, B, H, W, Cout, Kp, dtype, relu ? 1 : 0, stream, 0, direct);
+    }
+    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+    const int64_t M64 = (int64_t)B * Ho * Wo;
+    HGR_REQUIRE(M64 < (1ll << 31), "hgr_conv3x3_nhwc: too many output pixels");
+    GemmArgs a = gemm_args(x, 0, w, Kp, out, Cout, (int)M64, Cout, Kp, true, 0);
+    a.bias = bias; a.m_fastest = 0;
+    a.cH = H; a.cW = W; a.cC = C; a.cStride = stride; a.cHo = Ho; a.cWo = Wo;
+    a.cMagic = (unsigned)(((1ull << 32) + (unsigned)C - 1) / (unsigned)C);
+    a.cUni = (C % 64 == 0) ? 1 : 0;
+    const GemmLaunch L = plan_conv3x3(a, (int64_t)B * H * W, relu, hgr_aligned(out, 16));
+    return gemm_run("hgr_conv3x3_nhwc", a, &L, 1, dtype, stream);
+}
+}  // namespace
 
 extern "C" int hgr_conv3x3_nhwc(const void *x, const void *w, const float *bias, void *out,
                                 int B, int H, int W, int C, int Cout, int stride, int Kp, int dtype, void *stream) {
@@ -342,6 +427,7 @@ extern "C" int hgr_conv3x3_nhwc_plain(const void *x, const void *w, void *out, i
 
 extern "C" int hgr_gemm_nt_splitk(const void *A, int64_t lda, const void *W, int64_t ldw, float *partial, int64_t ldc,
                                   int M, int N, int K, int kc, int dtype, void *stream) {
+    CaptureScope capture;
     HGR_REQUIRE(A && W && partial, "hgr_gemm_nt_splitk: null operand");
     HGR_REQUIRE(M >= 1 && N >= 1 && K >= BK && K % BK == 0 && kc >= BK && kc % BK == 0, "hgr_gemm_nt_splitk: bad shape M=%d N=%d K=%d kc=%d", M, N, K, kc);
     HGR_REQUIRE(lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0 && hgr_aligned(A, 16) && hgr_aligned(W, 16), "hgr_gemm_nt_splitk: operands must be 16-byte aligned with leading dimensions %% 8 == 0");
@@ -349,24 +435,13 @@ extern "C" int hgr_gemm_nt_splitk(const void *A, int64_t lda, const void *W, int
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_gemm_nt_splitk: bad dtype %d", dtype);
     const int S = (K + kc - 1) / kc;
     HGR_REQUIRE(S <= 65535, "hgr_gemm_nt_splitk: %d splits exceed the grid limit", S);
-    GemmArgs a;
-    a.A = (const char *)A; a.lda = lda; a.W = (const char *)W; a.ldw = ldw;
-    a.C = partial; a.ldc = ldc; a.bias = nullptr; a.res = nullptr; a.ldr = 0;
-    a.M = M; a.N = N; a.K = K;
-    a.tiles_m = (M + BM - 1) / BM; a.tiles_n = (N + BN - 1) / BN;
-    a.m_fastest = 0; a.vec_ok = 1; a.dbg = 0; a.kc = kc; a.csplit = (int64_t)M * ldc;
-    a.cH = a.cW = a.cC = a.cStride = a.cHo = a.cWo = 0; a.cMagic = 0; a.cUni = 0;
+    GemmArgs a = gemm_args(A, lda, W, ldw, partial, ldc, M, N, K, true, 0);
+    a.m_fastest = 0; a.kc = kc; a.csplit = (int64_t)M * ldc;
     // every slice at least 2 K-tiles deep and an output of at least one 256^2 tile: the deep-pipelined kernel
-    const bool big = hgr_gemm_force_tile() != 128 && M >= 256 && N >= 256 && kc >= 128 && (K - (S - 1) * kc) >= 128;
-    if (big) {
-        a.tiles_m = (M + 255) / 256; a.tiles_n = (N + 255) / 256;
-        launch_256(a, dtype, HGR_EPI_NONE, true, false, dim3((unsigned)(a.tiles_m * a.tiles_n), (unsigned)S), (hipStream_t)stream);
-        HGR_CHECK_LAUNCH("hgr_gemm_nt_splitk");
-        return HGR_OK;
-    }
-    launch_128(a, dtype, HGR_EPI_NONE, true, V128_PLAIN, dim3((unsigned)(a.tiles_m * a.tiles_n), (unsigned)S), (hipStream_t)stream);
-    HGR_CHECK_LAUNCH("hgr_gemm_nt_splitk");
-    return HGR_OK;
+    const bool big = k_tile.get() != 128 && M >= 256 && N >= 256 && kc >= 128 && (K - (S - 1) * kc) >= 128;
+    const GemmLaunch L = big ? plan_tiles(HGR_KERNEL_256, 0, HGR_EPI_NONE, true, M, N, 256, 256, (unsigned)S)
+                             : plan_tiles(HGR_KERNEL_128, V128_PLAIN, HGR_EPI_NONE, true, M, N, BM, BN, (unsigned)S);
+    return gemm_run("hgr_gemm_nt_splitk", a, &L, 1, dtype, stream);
 }
 
 // ---- LayerNorm folded into the GEMMs around it --------------------------------------------------------------------------
@@ -379,13 +454,6 @@ int ln_common_checks(const char *who, const void *A, int64_t lda, const void *W,
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "%s: bad dtype %d", who, dtype);
     return HGR_OK;
 }
-void ln_args(GemmArgs &a, const void *A, int64_t lda, const void *W, int64_t ldw, void *C, int64_t ldc, int M, int N, int K) {
-    a.A = (const char *)A; a.lda = lda; a.W = (const char *)W; a.ldw = ldw; a.C = C; a.ldc = ldc; a.bias = nullptr; a.res = nullptr; a.ldr = 0;
-    a.M = M; a.N = N; a.K = K; a.tiles_m = (M + 255) / 256; a.tiles_n = N / 128;
-    a.m_fastest = ((int64_t)N * K > (int64_t)M * K) ? 1 : 0; a.vec_ok = 1; a.dbg = duo_dbg(); a.kc = 0; a.csplit = 0; a.group = duo_group();
-    a.cH = a.cW = a.cC = a.cStride = a.cHo = a.cWo = 0; a.cMagic = 0; a.cUni = 0;
-    a.ln_stats = nullptr; a.ln_slots = 0; a.ln_eps = 0.f; a.ln_xh = a.ln_xl = nullptr; a.ln_ldx = 0; a.ln_s = a.ln_c = nullptr; a.ln_flag = nullptr; a.ln_guard = 0.f;
-}
 }  // namespace
 
 extern "C" int hgr_gemm_nt_res_stats(const void *A, int64_t lda, const void *W, int64_t ldw, void *xh, void *xl, int64_t ldx,
@@ -396,32 +464,26 @@ extern "C" int hgr_gemm_nt_res_stats(const void *A, int64_t lda, const void *W, 
 extern "C" int hgr_gemm_nt_res_stats_guard(const void *A, int64_t lda, const void *W, int64_t ldw, void *xh, void *xl, int64_t ldx,
                                            const float *bias, float *stats, float guard_sumsq, uint32_t *flag,
                                            int M, int N, int K, int dtype, void *stream) {
+    CaptureScope capture;
     if (int rc = ln_common_checks("hgr_gemm_nt_res_stats", A, lda, W, ldw, M, N, K, dtype)) return rc;
     HGR_REQUIRE(!flag || (guard_sumsq > 0.f && hgr_aligned(flag, 4)), "hgr_gemm_nt_res_stats_guard: flag needs guard_sumsq > 0 and 4-byte alignment");
     HGR_REQUIRE(xh && xl && bias && stats, "hgr_gemm_nt_res_stats: null xh / xl / bias / stats");
     // the interior epilogue reads and writes the pair with 16-byte accesses (8 columns per lane) at 32-bit offsets of up to 127 rows
     HGR_REQUIRE(ldx >= N && ldx % 8 == 0 && ldx < (1 << 23) && hgr_aligned(xh, 16) && hgr_aligned(xl, 16), "hgr_gemm_nt_res_stats: xh / xl must be 16-byte aligned, ldx %% 8 == 0, ldx < 2^23");
     HGR_REQUIRE(hgr_aligned(bias, 16) && hgr_aligned(stats, 8), "hgr_gemm_nt_res_stats: bias must be 16-byte, stats 8-byte aligned");
-    GemmArgs a;
-    ln_args(a, A, lda, W, ldw, nullptr, 0, M, N, K);
+    GemmArgs a = gemm_args(A, lda, W, ldw, nullptr, 0, M, N, K, true, duo_dbg());
     a.bias = bias;
     a.ln_stats = stats; a.ln_slots = N / 64; a.ln_xh = xh; a.ln_xl = xl; a.ln_ldx = ldx;
     a.ln_flag = flag; a.ln_guard = guard_sumsq;
-    if (ws_enabled() && hgr_gemm_force_tile() == 0 && ws_covers(M, N, K, WS_LNP)) {
-        launch_ws(a, dtype, WS_LNP, 0, true, (hipStream_t)stream);
-        HGR_CHECK_LAUNCH("hgr_gemm_nt_res_stats");
-        return HGR_OK;
-    }
-    dim3 grid;
-    duo_apply_plan(a, true, grid);
-    launch_duo(a, dtype, HGR_EPI_BIAS_RESIDUAL, true, 1, grid, (hipStream_t)stream);
-    HGR_CHECK_LAUNCH("hgr_gemm_nt_res_stats");
-    return HGR_OK;
+    const GemmLaunch L = k_ws.get() && k_tile.get() == 0 && ws_covers(M, N, K, WS_LNP) ? plan_ws(M, N, WS_LNP, HGR_EPI_BIAS_RESIDUAL, 0)
+                                                                                        : plan_duo(a, 1, HGR_EPI_BIAS_RESIDUAL, true);
+    return gemm_run("hgr_gemm_nt_res_stats", a, &L, 1, dtype, stream);
 }
 
 extern "C" int hgr_gemm_nt_ln(const void *X16, int64_t ldx, const void *Wfold, int64_t ldw, void *C, int64_t ldc,
                               const float *ln_s, const float *ln_c, const float *stats, float eps,
                               int M, int N, int K, int dtype, int act, void *stream) {
+    CaptureScope capture;
     if (int rc = ln_common_checks("hgr_gemm_nt_ln", X16, ldx, Wfold, ldw, M, N, K, dtype)) return rc;
     HGR_REQUIRE(C && ln_s && ln_c && stats, "hgr_gemm_nt_ln: null C / ln_s / ln_c / stats");
     HGR_REQUIRE(K % 128 == 0, "hgr_gemm_nt_ln: the row width K=%d must be a multiple of 128 (two 64-column statistic slots per 16-byte load)", K);
@@ -429,57 +491,40 @@ extern "C" int hgr_gemm_nt_ln(const void *X16, int64_t ldx, const void *Wfold, i
     HGR_REQUIRE(ldc >= N && ldc % 8 == 0 && ldc < (1 << 23) && hgr_aligned(C, 16), "hgr_gemm_nt_ln: C must be 16-byte aligned with ldc %% 8 == 0, ldc < 2^23");
     HGR_REQUIRE(hgr_aligned(ln_s, 16) && hgr_aligned(ln_c, 16) && hgr_aligned(stats, 16), "hgr_gemm_nt_ln: ln_s / ln_c / stats must be 16-byte aligned");
     HGR_REQUIRE(act == 0 || act == 1, "hgr_gemm_nt_ln: act must be 0 (none) or 1 (QuickGELU), got %d", act);
-    GemmArgs a;
-    ln_args(a, X16, ldx, Wfold, ldw, C, ldc, M, N, K);
+    GemmArgs a = gemm_args(X16, ldx, Wfold, ldw, C, ldc, M, N, K, true, duo_dbg());
     a.ln_stats = const_cast<float *>(stats); a.ln_slots = K / 64; a.ln_eps = eps; a.ln_s = ln_s; a.ln_c = ln_c;
-    if (hgr_gemm_force_tile() == 0 && p8_wanted(M, N, K)) {
-        launch_p8(a, dtype, act, (hipStream_t)stream);
-        HGR_CHECK_LAUNCH("hgr_gemm_nt_ln");
-        return HGR_OK;
-    }
-    if (ws_enabled() && hgr_gemm_force_tile() == 0 && ws_covers(M, N, K, WS_LNC)) {
-        launch_ws(a, dtype, WS_LNC, act, false, (hipStream_t)stream);
-        HGR_CHECK_LAUNCH("hgr_gemm_nt_ln");
-        return HGR_OK;
-    }
-    dim3 grid;
-    duo_apply_plan(a, true, grid);
-    launch_duo(a, dtype, act ? HGR_EPI_BIAS_QUICKGELU : HGR_EPI_BIAS, false, 2, grid, (hipStream_t)stream);
-    HGR_CHECK_LAUNCH("hgr_gemm_nt_ln");
-    return HGR_OK;
+    const int epi = act ? HGR_EPI_BIAS_QUICKGELU : HGR_EPI_BIAS;
+    const GemmLaunch L = k_tile.get() == 0 && p8_wanted(M, N, K)                           ? plan_p8(M, N, act)
+                         : k_ws.get() && k_tile.get() == 0 && ws_covers(M, N, K, WS_LNC) ? plan_ws(M, N, WS_LNC, epi, act)
+                                                                                          : plan_duo(a, 2, epi, false);
+    return gemm_run("hgr_gemm_nt_ln", a, &L, 1, dtype, stream);
 }
 
 extern "C" int hgr_gemm_nt_bias_gelu_dual(const void *A, int64_t lda, const void *W, int64_t ldw, void *pre, int64_t ldpre, void *post, int64_t ldpost,
                                           const float *bias, int M, int N, int K, int dtype, void *stream) {
+    CaptureScope capture;
     if (int rc = ln_common_checks("hgr_gemm_nt_bias_gelu_dual", A, lda, W, ldw, M, N, K, dtype)) return rc;
     HGR_REQUIRE(pre && post && bias, "hgr_gemm_nt_bias_gelu_dual: null pre / post / bias");
     HGR_REQUIRE(ldpre >= N && ldpost >= N && ldpre % 8 == 0 && ldpost % 8 == 0 && ldpre < (1 << 23) && ldpost < (1 << 23) && hgr_aligned(pre, 16) && hgr_aligned(post, 16) && hgr_aligned(bias, 16),
                 "hgr_gemm_nt_bias_gelu_dual: pre / post / bias must be 16-byte aligned, leading dimensions >= N, %% 8 == 0, < 2^23");
-    GemmArgs a;
-    ln_args(a, A, lda, W, ldw, pre, ldpre, M, N, K);
+    GemmArgs a = gemm_args(A, lda, W, ldw, pre, ldpre, M, N, K, true, duo_dbg());
     a.bias = bias; a.ln_xh = post; a.ln_ldx = ldpost;
-    dim3 grid;
-    duo_apply_plan(a, true, grid);
-    launch_duo(a, dtype, HGR_EPI_BIAS, false, 4, grid, (hipStream_t)stream);
-    HGR_CHECK_LAUNCH("hgr_gemm_nt_bias_gelu_dual");
-    return HGR_OK;
+    const GemmLaunch L = plan_duo(a, 4, HGR_EPI_BIAS, false);
+    return gemm_run("hgr_gemm_nt_bias_gelu_dual", a, &L, 1, dtype, stream);
 }
 
 extern "C" int hgr_gemm_nt_qgelu_grad_colsum(const void *A, int64_t lda, const void *W, int64_t ldw, void *C, int64_t ldc, const void *pre, int64_t ldpre,
                                              float *colsum_part, int M, int N, int K, int dtype, void *stream) {
+    CaptureScope capture;
     if (int rc = ln_common_checks("hgr_gemm_nt_qgelu_grad_colsum", A, lda, W, ldw, M, N, K, dtype)) return rc;
     HGR_REQUIRE(C && pre && colsum_part, "hgr_gemm_nt_qgelu_grad_colsum: null C / pre / colsum_part");
     HGR_REQUIRE(ldc >= N && ldpre >= N && ldc % 8 == 0 && ldpre % 8 == 0 && ldc < (1 << 20) && ldpre < (1 << 20) && hgr_aligned(C, 16) && hgr_aligned(pre, 16) && hgr_aligned(colsum_part, 16),
                 "hgr_gemm_nt_qgelu_grad_colsum: C / pre / colsum_part must be 16-byte aligned, leading dimensions >= N, %% 8 == 0, < 2^20");
-    GemmArgs a;
-    ln_args(a, A, lda, W, ldw, C, ldc, M, N, K);
+    GemmArgs a = gemm_args(A, lda, W, ldw, C, ldc, M, N, K, true, duo_dbg());
     a.res = (const float *)pre; a.ldr = ldpre;
     a.colsum = colsum_part; a.colsum_units = (M + 63) / 64;
-    dim3 grid;
-    duo_apply_plan(a, true, grid);
-    launch_duo(a, dtype, HGR_EPI_QGELU_GRAD16, false, 0, grid, (hipStream_t)stream);
-    HGR_CHECK_LAUNCH("hgr_gemm_nt_qgelu_grad_colsum");
-    return HGR_OK;
+    const GemmLaunch L = plan_duo(a, 0, HGR_EPI_QGELU_GRAD16, false);
+    return gemm_run("hgr_gemm_nt_qgelu_grad_colsum", a, &L, 1, dtype, stream);
 }
 
 // ---- logits GEMM with the evaluation consumers in its epilogue ------------------------------------------------------------
@@ -522,7 +567,7 @@ static int logits_eval_stages(int stages, const void *feat16, const void *zsl_pe
     SlabArgs a;
     a.A = (const char *)feat16; a.lda = D; a.W = (const char *)zsl_perm16; a.ldw = D; a.M = rows; a.K = D; a.Np = n_perm;
     a.tpos = tpos_perm; a.epos = epos_perm; a.S = S;
-    { static int d = -1; if (d < 0) d = hgr_lab_env("HGR_LS_DBG"); a.dbg = d; }
+    { static const int d = hgr_lab_env("HGR_LS_DBG"); a.dbg = d; }
     a.ev_key = (unsigned long long *)workspace;
     a.ev_tmax = (float *)((char *)workspace + (size_t)rows * S * 8);
     a.ev_p1 = (int *)((char *)workspace + (size_t)rows * S * 16);

@@ -18,44 +18,56 @@ namespace hgr_gemm {
 constexpr int BK = 64;
 
 struct GemmArgs {
-    const char *A; int64_t lda;
-    const char *W; int64_t ldw;
-    void *C; int64_t ldc;
-    const float *bias;
-    const float *res; int64_t ldr;
-    int M, N, K;
-    int tiles_m, tiles_n;
-    int m_fastest;   // 1: consecutive tile ids walk M first (W panel shared), 0: walk N first
-    int vec_ok;      // C / residual rows allow 4-element vector access
-    int dbg;         // diagnostics only (HGR_GEMM_DBG): 1 = skip MFMAs, 2 = skip LDS-DMA issue, 3 = skip epilogue
+    const char *A = nullptr; int64_t lda = 0;
+    const char *W = nullptr; int64_t ldw = 0;
+    void *C = nullptr; int64_t ldc = 0;
+    const float *bias = nullptr;
+    const float *res = nullptr; int64_t ldr = 0;
+    int M = 0, N = 0, K = 0;
+    int tiles_m = 0, tiles_n = 0;
+    int m_fastest = 0;   // 1: consecutive tile ids walk M first (W panel shared), 0: walk N first
+    int vec_ok = 0;  // C / residual rows allow 4-element vector access
+    int dbg = 0;     // diagnostics only (HGR_GEMM_DBG): 1 = skip MFMAs, 2 = skip LDS-DMA issue, 3 = skip epilogue
     // implicit-GEMM 3x3 convolution (CONV kernels only): A is an NHWC image [B, H, W, C], pad 1
-    int cH, cW, cC, cStride, cHo, cWo;
-    unsigned cMagic;  // ceil(2^32 / cC): __umulhi(k, cMagic) == k / cC for every k < 9 * cC + 64 (k * cC < 2^32)
-    int cUni;         // cC % 64 == 0: a 64-deep K-tile lies inside ONE tap, so tap / kernel offset are wave-uniform per K-tile (scalar ALU)
+    int cH = 0, cW = 0, cC = 0, cStride = 0, cHo = 0, cWo = 0;
+    unsigned cMagic = 0;  // ceil(2^32 / cC): __umulhi(k, cMagic) == k / cC for every k < 9 * cC + 64 (k * cC < 2^32)
+    int cUni = 0;     // cC % 64 == 0: a 64-deep K-tile lies inside ONE tap, so tap / kernel offset are wave-uniform per K-tile (scalar ALU)
     // split-K (gemm_nt_128 only): blockIdx.y = split s works on K columns [s * kc, min(K, (s + 1) * kc)) and writes its own
     // fp32 partial C + s * csplit elements; 0 = off
-    int kc; int64_t csplit;
+    int kc = 0; int64_t csplit = 0;
     // LayerNorm folded into the GEMMs around it (gemm_nt_duo only, LN template parameter):
     //   producer (LN = 1, x += A W^T + b): the residual stream is kept as a 16-bit pair (hi, lo) with x = hi + lo - 4 bytes per
     //            element like fp32, and hi IS the next GEMM's A operand; per row and 64-column slot it also emits the partial
     //            (sum, sum of squares) of the new values -> ln_stats [M][ln_slots][2]
     //   consumer (LN = 2, y = LN(x) W^T + b): A is the un-normalised 16-bit x, W the gamma-folded weight,
     //            y = rstd_m (acc - mean_m ln_s[n]) + ln_c[n] with row statistics from ln_stats (K = row width)
-    float *ln_stats; int ln_slots; float ln_eps;
-    void *ln_xh, *ln_xl; int64_t ln_ldx;      // producer: the residual stream as a 16-bit PAIR, x = hi + lo (hi in the MFMA type, lo f16)
-    const float *ln_s, *ln_c;
+    float *ln_stats = nullptr; int ln_slots = 0; float ln_eps = 0.f;
+    void *ln_xh = nullptr, *ln_xl = nullptr; int64_t ln_ldx = 0;      // producer: the residual stream as a 16-bit PAIR, x = hi + lo (hi in the MFMA type, lo f16)
+    const float *ln_s = nullptr, *ln_c = nullptr;
     // producer range guard: when a 64-column slot's sum of squares exceeds ln_guard (or is inf / NaN) its bit pattern is
     // atomicMax'ed into *ln_flag (0 = the stream stayed in range); null = no guard
-    unsigned *ln_flag; float ln_guard;
-    int group;       // gemm_nt_duo: row (or column) panels per raster group (HGR_GEMM_GROUP, default 4)
+    unsigned *ln_flag = nullptr; float ln_guard = 0.f;
+    int group = 0;   // gemm_nt_duo: row (or column) panels per raster group (HGR_GEMM_GROUP, default 4)
     // gemm_nt_duo tail plan (duo_plan): blocks [0, nbig) = full 256 x 128 tiles on row panels [0, big_panels), the remaining blocks =
     // 128 x 128 half tiles on the rows behind them (tiles_m_half panels of 128 rows).  No tail: nbig = grid, big_panels = tiles_m.
-    int nbig, big_panels, tiles_m_half;
+    int nbig = 0, big_panels = 0, tiles_m_half = 0;
     // HGR_EPI_QGELU_GRAD16 on gemm_nt_duo only (hgr_gemm_nt_qgelu_grad_colsum): column sums of the ROUNDED 16-bit outputs per 64-row
     // unit, colsum[unit][n] for unit < colsum_units = ceil(M / 64) - the bias gradient of the layer below without a second pass over C
     float *colsum = nullptr; int colsum_units = 0;
-    int total = 0;   // gemm_nt_duo, persistent form: number of virtual blocks (0 = gridDim.x, one tile per workgroup); set by launch_duo
+    int total = 0;   // gemm_nt_duo, persistent form: number of virtual blocks (0 = gridDim.x, one tile per workgroup); gemm_nt_ws: its tile count
 };
+
+// The part of the argument block every host entry point fills alike; the entry point then sets only what is specific to it.
+// m_fastest: each XCD owns a contiguous range of tile ids; the operand indexed by the slow tile index is fetched ~once, the other one
+// once per XCD.  Make the bigger operand the once-fetched one.
+inline int gemm_m_fastest(int M, int N, int K) { return (int64_t)N * K > (int64_t)M * K ? 1 : 0; }
+inline GemmArgs gemm_args(const void *A, int64_t lda, const void *W, int64_t ldw, void *C, int64_t ldc, int M, int N, int K, bool vec_ok, int dbg) {
+    GemmArgs a;
+    a.A = (const char *)A; a.lda = lda; a.W = (const char *)W; a.ldw = ldw; a.C = C; a.ldc = ldc;
+    a.M = M; a.N = N; a.K = K;
+    a.m_fastest = gemm_m_fastest(M, N, K); a.vec_ok = vec_ok ? 1 : 0; a.dbg = dbg;
+    return a;
+}
 
 
 // 16 zero bytes every out-of-bounds conv tap (and the K padding) is loaded from; one copy per translation unit (no -fgpu-rdc)
@@ -305,33 +317,29 @@ void launch_128(const GemmArgs &a, int dtype, int epi, bool out32, int variant, 
 // gemm_nt_256: plain (any epi) or the implicit-GEMM convolution (BIAS_RELU, 16-bit out)
 void launch_256(const GemmArgs &a, int dtype, int epi, bool out32, bool conv, dim3 grid, hipStream_t s);
 // gemm_nt_duo: ln = 0 plain (any epi), 1 LayerNorm producer, 2 LayerNorm consumer (epi BIAS / BIAS_QUICKGELU), 4 dual output
-// (pre-activation + QuickGELU), 5 the 3 x 3 convolution
+// (pre-activation + QuickGELU), 5 the 3 x 3 convolution.  ln = 1 walks a.total > grid.x virtual blocks (plan_duo, hgr_gemm.hip)
 void launch_duo(const GemmArgs &a, int dtype, int epi, bool out32, int ln, dim3 grid, hipStream_t s);
-int duo_set_persist(int enabled);     // hgr_gemm_set_persist
 // gemm_nt_ws (hgr_gemm_ws.hip): 256 x 128 tiles, ONE persistent workgroup per CU of 4 matrix waves + 4 helper waves; the epilogue of
 // tile i runs in the helper waves under the MFMAs of tile i + 1.  Same bits as gemm_nt_duo.  mode WS_PLAIN: 16-bit C = act(A W^T
 // [+ bias]), act 0 none / 1 QuickGELU / 2 ReLU; WS_LNC: the folded-LayerNorm consumer (act 0 / 1); WS_LNP: the residual producer.
 enum { WS_PLAIN = 0, WS_LNC = 1, WS_LNP = 2 };
 bool ws_covers(int M, int N, int K, int mode);      // whole tiles, an even number >= 12 of K-tiles, at least one tile per CU
-void launch_ws(const GemmArgs &a, int dtype, int mode, int act, bool hasb, hipStream_t s);
-int ws_enabled();                     // HGR_WS (default 0: an experiment that did not beat gemm_nt_duo, kept bit-identical and tested)
-int ws_set(int enabled);              // hgr_gemm_set_ws
+int ws_cus();                         // workgroups of a launch: the CUs in whole multiples of the 8 XCDs
+void launch_ws(const GemmArgs &a, int dtype, int mode, int act, bool hasb, dim3 grid, hipStream_t s);
 // hgr_gemm_p8.hip: the LayerNorm-folded consumer as one persistent 512-thread workgroup per CU on 256 x 256 tiles
 bool p8_covers(int M, int N, int K);
-void launch_p8(const GemmArgs &a, int dtype, int act, hipStream_t s);
-bool p8_wanted(int M, int N, int K);  // by shape, or as forced by HGR_P8 / hgr_gemm_set_p8
-int p8_set(int mode);                 // hgr_gemm_set_p8: 0 never, 1 wherever it covers, 2 by shape (default)
+void launch_p8(const GemmArgs &a, int dtype, int act, dim3 grid, hipStream_t s);
 
 // first stage of hgr_logits_eval (hgr_logits_slab.hip): 512-row x 96-column tiles, one per CU, evaluation consumers in the epilogue
 struct SlabArgs {
-    const char *A; int64_t lda;          // features [M, K] 16-bit
-    const char *W; int64_t ldw;          // level-sorted class matrix [Np, K] 16-bit, Np % 96 == 0
-    int M, K, Np;
-    const int *tpos, *epos;              // [Np] train / test position of every permuted column (-1 = not in the subset / padding)
-    unsigned long long *ev_key;          // [M][S]      S = Np / 32
-    float *ev_tmax, *ev_m2; int *ev_p1;  // [M][S][2]
-    int S;
-    int dbg;                             // HGR_LS_DBG (timing experiments only, wrong results): 1 skip the MFMAs, 2 skip the feature DMAs, 4 skip the class-row DMAs, 8 skip the epilogue, 16 skip the warm-up touches
+    const char *A = nullptr; int64_t lda = 0;          // features [M, K] 16-bit
+    const char *W = nullptr; int64_t ldw = 0;          // level-sorted class matrix [Np, K] 16-bit, Np % 96 == 0
+    int M = 0, K = 0, Np = 0;
+    const int *tpos = nullptr, *epos = nullptr;              // [Np] train / test position of every permuted column (-1 = not in the subset / padding)
+    unsigned long long *ev_key = nullptr;          // [M][S]      S = Np / 32
+    float *ev_tmax = nullptr, *ev_m2 = nullptr; int *ev_p1 = nullptr;  // [M][S][2]
+    int S = 0;
+    int dbg = 0;                             // HGR_LS_DBG (timing experiments only, wrong results): 1 skip the MFMAs, 2 skip the feature DMAs, 4 skip the class-row DMAs, 8 skip the epilogue, 16 skip the warm-up touches
 };
 void launch_logits_slab(const SlabArgs &a, int dtype, hipStream_t s);
 

@@ -1037,37 +1037,7 @@ void launch_duo_dt(const GemmArgs &a, int epi, bool out32, int ln, dim3 grid, hi
 }
 }  // namespace
 
-// Default: at most two workgroups per CU, each walking its share of the tiles (see gemm_nt_duo); HGR_DUO_PERSIST=0 = one workgroup per
-// tile (A/B runs).  Measured on the ViT-B/32 evaluation step, interleaved pairs on one box: every launch persistent 5.064 -> 5.008 ms
-// (-1.1 %; by shape proj 128.6 -> 123.5 us, out 50.1 -> 48.5, fc unchanged), the producers only 5.137 -> 5.104 (-0.6 %).  Bit-identical.
-static int g_duo_persist = -1;                   // hgr_gemm_set_persist / HGR_DUO_PERSIST
-static int duo_persist() {
-    if (g_duo_persist < 0) { const char *e = getenv("HGR_DUO_PERSIST"); g_duo_persist = e ? (atoi(e) != 0) : 1; }
-    return g_duo_persist;
-}
-int duo_set_persist(int enabled) { const int prev = duo_persist(); g_duo_persist = enabled; return prev; }
-static int duo_slots() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? 2 * pr.multiProcessorCount : 512;
-        n &= ~7;                 // whole multiples of the 8 XCDs: virtual block v and physical block v % grid sit on the same XCD
-        if (n < 8) n = 8;
-    }
-    return n;
-}
-
-void launch_duo(const GemmArgs &a0, int dtype, int epi, bool out32, int ln, dim3 grid, hipStream_t s) {
-    GemmArgs a = a0;
-    a.total = 0;
-    // ... for the residual producers (ln == 1, the only instantiations compiled with the tile loop) on launches of up to two rounds of
-    // the chip's slots - the launches that gain (their epilogue's read-modify-write drains beside the next tile's first operand loads).
-    // Launches of many rounds LOSE with the static deal (ViT-L/14 training step 221.2 -> 223.6 ms, RN50 step 9.58 -> 9.66 ms with
-    // every launch persistent): the dispatcher's first-free-slot order balances the slots' drifting speeds, the fixed stride does not;
-    // the consumer / plain launches of one to two rounds measured neutral to slightly negative (RN50 9.97 -> 10.03 ms).
-    const int ds = duo_slots();
-    if (duo_persist() && ln == 1 && grid.y == 1 && !a.kc && (int)grid.x > ds && (int)grid.x <= 2 * ds) { a.total = (int)grid.x; grid.x = (unsigned)ds; }
+void launch_duo(const GemmArgs &a, int dtype, int epi, bool out32, int ln, dim3 grid, hipStream_t s) {
     if (dtype == HGR_BF16) launch_duo_dt<HGR_BF16>(a, epi, out32, ln, grid, s);
     else launch_duo_dt<HGR_F16>(a, epi, out32, ln, grid, s);
 }

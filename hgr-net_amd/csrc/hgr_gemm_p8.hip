@@ -254,46 +254,16 @@ __global__ __launch_bounds__(P8_NT) void gemm_nt_p8(GemmArgs p) {
   }
 }
 
-int g_p8 = -1;                  // hgr_gemm_set_p8 / HGR_P8: 0 never, 1 wherever p8_covers, 2 by shape (p8_wanted; the default)
-int p8_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    }
-    return n;
-}
 }  // namespace
-
-int p8_mode() {
-    if (g_p8 < 0) { const char *e = getenv("HGR_P8"); const int v = e ? atoi(e) : 2; g_p8 = v >= 0 && v <= 2 ? v : 2; }
-    return g_p8;
-}
-int p8_set(int mode) { const int prev = p8_mode(); g_p8 = mode; return prev; }
-
-// By shape: measured against gemm_nt_duo (tools/p8_bench.py, back to back, one MI355X, bit-identical): 25 600 x 3 072 x 3 072
-// 436 -> 394 us (1 108 -> 1 228 TF/s), ViT-L/14's c_fc 65 536 x 4 096 x 1 024 543 -> 519, ViT-B/32's c_fc (K = 768, 4.7 tiles per CU)
-// 128.0 -> 126.2 back to back and 132.5 -> 131.8 in the step (the step itself unchanged), its k / v projection (2.3 tiles per CU)
-// 70.9 -> 74.3: a K-tile of this form takes ~3 400 clocks where fill, matrix and LDS time are ~2 000 each (ablation builds at
-// K = 3 072: 390 us; no fragment reads 378; no LDS-DMA behind the prologue 318; neither 274 - the fill that does not overlap is
-// added), and a tile's prologue and epilogue run beside nothing - so it pays with long K and many tiles per CU only.
-bool p8_wanted(int M, int N, int K) {
-    const int m = p8_mode();
-    if (!m || !p8_covers(M, N, K)) return false;
-    return m == 1 || (K >= 1024 && (int64_t)(M / 256) * (N / 256) >= 4 * p8_cus());
-}
 
 // whole 256 x 256 tiles, an even number of K-tiles, at least one tile per CU (fewer: gemm_nt_duo's 512 slots fill the chip better)
 bool p8_covers(int M, int N, int K) {
-    return M % 256 == 0 && N % 256 == 0 && K % 128 == 0 && K >= 256 && (int64_t)(M / 256) * (N / 256) >= p8_cus();
+    return M % 256 == 0 && N % 256 == 0 && K % 128 == 0 && K >= 256 && (int64_t)(M / 256) * (N / 256) >= hgr_cu_count();
 }
 
-void launch_p8(const GemmArgs &a0, int dtype, int act, hipStream_t s) {
-    GemmArgs a = a0;
-    a.tiles_m = a.M / 256; a.tiles_n = a.N / 256;
-    const int tiles = a.tiles_m * a.tiles_n;
-    const dim3 grid((unsigned)(tiles < p8_cus() ? tiles : p8_cus())), block(P8_NT);
+// the caller planned the launch (plan_p8, hgr_gemm.hip: whole tiles, at most one workgroup per CU)
+void launch_p8(const GemmArgs &a, int dtype, int act, dim3 grid, hipStream_t s) {
+    const dim3 block(P8_NT);
     if (dtype == HGR_BF16) {
         if (act) hipLaunchKernelGGL((gemm_nt_p8<HGR_BF16, 1>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((gemm_nt_p8<HGR_BF16, 0>), grid, block, 0, s, a);

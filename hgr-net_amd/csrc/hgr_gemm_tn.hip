@@ -311,8 +311,9 @@ __global__ __launch_bounds__(512) void gemm_tn_256(TnArgs p) {
 }
 
 // tile plan of the linear product: 256 x 256 when both extents fill such tiles with <= 7 % more padded area than 128 x 128
+HgrKnob<> tn_tile_forced{"HGR_TN_TILE", 0};
 int tn_tile(int Na, int Nb) {
-    static const int forced = [] { const char *e = getenv("HGR_TN_TILE"); return e ? atoi(e) : 0; }();
+    const int forced = tn_tile_forced.get();
     if (forced == 128 || forced == 256) return forced;
     if (Na < 256 || Nb < 256) return 128;
     const int64_t big = (int64_t)((Na + 255) / 256) * ((Nb + 255) / 256) * 65536, small = (int64_t)((Na + 127) / 128) * ((Nb + 127) / 128) * 16384;

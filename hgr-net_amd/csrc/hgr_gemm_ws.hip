@@ -552,26 +552,10 @@ __global__ __launch_bounds__(WS_NT) void gemm_nt_ws(GemmArgs p) {
 }
 }  // namespace
 
-static int ws_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-        n &= ~7;
-        if (n < 8) n = 8;
-    }
-    return n;
+int ws_cus() {
+    const int n = hgr_cu_count() & ~7;
+    return n < 8 ? 8 : n;
 }
-
-static int g_ws = -1;                            // hgr_gemm_set_ws / HGR_WS
-int ws_enabled() {
-    // default OFF: measured equal to or slower than gemm_nt_duo on every tower shape (profiles/NOTES.md, round 5) - the epilogue's
-    // vector instructions cost their SIMD's matrix wave the same issue slots whichever wave executes them, and LDS bandwidth bounds both
-    if (g_ws < 0) { const char *e = getenv("HGR_WS"); g_ws = e ? (atoi(e) != 0) : 0; }
-    return g_ws;
-}
-int ws_set(int enabled) { const int prev = ws_enabled(); g_ws = enabled; return prev; }
 
 // Whether the role-split kernel covers a launch: whole 256 x 128 tiles, an even number (>= 12) of K-tiles, at least one tile per CU
 // (shorter launches keep gemm_nt_duo and its tail plan), 16-bit rows addressable as in gemm_nt_duo
@@ -620,15 +604,11 @@ static void ws_launch_dt(const GemmArgs &a, int mode, int act, bool hasb, dim3 g
     else ws_launch_one<DT, WS_PLAIN, 0, true, 0>(a, g, s);
 }
 
-// mode WS_PLAIN: act 0 none / 1 QuickGELU / 2 ReLU, hasb = bias; WS_LNC: act 0 / 1; WS_LNP.  The caller checked ws_covers().
-void launch_ws(const GemmArgs &a0, int dtype, int mode, int act, bool hasb, hipStream_t s) {
-    GemmArgs a = a0;
-    a.tiles_m = a.M / 256; a.tiles_n = a.N / 128;
-    a.total = a.tiles_m * a.tiles_n;
-    int grid = ws_cus();
-    if (grid > a.total) grid = a.total;
-    if (dtype == HGR_BF16) ws_launch_dt<HGR_BF16>(a, mode, act, hasb, dim3((unsigned)grid), s);
-    else ws_launch_dt<HGR_F16>(a, mode, act, hasb, dim3((unsigned)grid), s);
+// mode WS_PLAIN: act 0 none / 1 QuickGELU / 2 ReLU, hasb = bias; WS_LNC: act 0 / 1; WS_LNP.  The caller checked ws_covers() and
+// planned the launch (plan_ws, hgr_gemm.hip: whole tiles, a.total of them, at most ws_cus() workgroups).
+void launch_ws(const GemmArgs &a, int dtype, int mode, int act, bool hasb, dim3 grid, hipStream_t s) {
+    if (dtype == HGR_BF16) ws_launch_dt<HGR_BF16>(a, mode, act, hasb, grid, s);
+    else ws_launch_dt<HGR_F16>(a, mode, act, hasb, grid, s);
 }
 
 }  // namespace hgr_gemm

@@ -517,35 +517,17 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
 }  // namespace
 
 // HGR_QA_PERSIST=0: one tile per workgroup (grid = tiles); default: one persistent workgroup per CU
-static int qa_persist() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("HGR_QA_PERSIST"); v = e ? atoi(e) : 1; }
-    return v;
-}
+static HgrKnob<> qa_persist{"HGR_QA_PERSIST", 1};
 // The two-head-half raster (QkvAttnArgs::hsplit), default on; HGR_QA_HSPLIT=0 = every XCD walks whole row tiles.  Measured on the
 // ViT-B/32 evaluation step (two interleaved rounds, one box): counter reads per launch 194 -> 155 MB, 112.3 -> 110.7 us, step 4.951 ->
 // 4.928 ms; bit-identical (a tile's arithmetic does not depend on where it runs).  The same split of gemm_nt_duo's raster (two column
 // halves x four row quarters for c_fc) changed neither its reads (207 -> 203 MB) nor its time and is not in the tree; profiles/NOTES.md
-static int qa_hsplit() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("HGR_QA_HSPLIT"); v = e ? atoi(e) : 1; }
-    return v;
-}
-static int qa_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) n = pr.multiProcessorCount;
-        else n = 256;
-    }
-    return n;
-}
+static HgrKnob<> qa_hsplit{"HGR_QA_HSPLIT", 1};
 
 void launch_qkv_attn(const QkvAttnArgs &a, int dtype, bool causal, hipStream_t s) {
     const int tiles = a.tiles_m * a.H;
     // (eight-XCD raster; a launch of fewer than 8 row tiles keeps the plain walk)
-    const dim3 grid((unsigned)(qa_persist() ? (tiles < qa_cus() ? tiles : qa_cus()) : tiles)), block(QA_NT);
+    const dim3 grid((unsigned)(qa_persist.get() ? (tiles < hgr_cu_count() ? tiles : hgr_cu_count()) : tiles)), block(QA_NT);
     if (dtype == HGR_BF16) {
         if (causal) hipLaunchKernelGGL((qkv_attn<HGR_BF16, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((qkv_attn<HGR_BF16, false>), grid, block, 0, s, a);
@@ -579,7 +561,7 @@ extern "C" int hgr_gemm_nt_ln_mha(const void *X16, int64_t ldx, const void *Wfol
     HGR_REQUIRE((int64_t)a.tiles_m * heads < (1ll << 31), "hgr_gemm_nt_ln_mha: grid too large");
     // ... where the folded weights do not fit an L2 beside the panels in flight anyway (>= 2 MB: width 768 = 3.5 MB); below that the split
     // only reads every row panel on two XCDs (text tower, width 512 = 1.5 MB: 111 -> 188 MB per launch, same time)
-    a.hsplit = (qa_hsplit() && heads % 2 == 0 && a.tiles_m >= 8 && 3ll * Wd * K * 2 >= (2ll << 20)) ? 2 : 1;
+    a.hsplit = (qa_hsplit.get() && heads % 2 == 0 && a.tiles_m >= 8 && 3ll * Wd * K * 2 >= (2ll << 20)) ? 2 : 1;
     launch_qkv_attn(a, dtype, causal != 0, (hipStream_t)stream);
     HGR_CHECK_LAUNCH("hgr_gemm_nt_ln_mha");
     return HGR_OK;

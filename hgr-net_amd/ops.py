@@ -256,6 +256,23 @@ def gemm_set_persist(enabled: bool) -> int:
     return prev
 
 
+def gemm_plan(fn) -> list:
+    """The launches ONE call of an NT-family entry point inside fn() would make (hgr_gemm_plan_capture): the call validates and plans,
+    launches nothing; one dict per launch, keyed like hgr_gemm_launch of include/hgr.h."""
+    lib = _lib.load()
+    out = (_lib.GemmLaunch * 4)()
+    rc = lib.hgr_gemm_plan_capture(out, len(out))
+    if rc:
+        raise _lib.HgrError(f"hgr_gemm_plan_capture failed ({rc}): {lib.hgr_last_error().decode()}")
+    try:
+        fn()
+    finally:                                     # a covered call has disarmed the thread; anything else must not leave it armed
+        unused = lib.hgr_gemm_plan_capture(None, 0)
+    if unused:
+        raise _lib.HgrError("gemm_plan: fn() made no call that hgr_gemm_plan_capture covers")
+    return [{name: getattr(rec, name) for name, _ in rec._fields_} for rec in out if rec.kernel]
+
+
 def im2col_patches(image: torch.Tensor, out: torch.Tensor, patch: int) -> torch.Tensor:
     b, c, r, r2 = image.shape
     assert c == 3 and r == r2 and image.dtype == torch.float32 and image.is_contiguous() and out.is_contiguous()

@@ -11,7 +11,8 @@
  *   - plain pointers and sizes only; every tensor argument is a raw DEVICE pointer, row-major;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); every call is asynchronous
  *     and stream-ordered, never synchronises and allocates no device memory.  The only process-wide mutable state is
- *     (a) the development knobs hgr_gemm_set_tile / hgr_gemm_set_tail / hgr_gemm_set_persist (plan overrides for A/B runs and tests) and
+ *     (a) the development knobs hgr_gemm_set_tile / hgr_gemm_set_tail / hgr_gemm_set_persist / hgr_gemm_set_ws / hgr_gemm_set_p8 (plan
+ *         overrides for A/B runs and tests; hgr_gemm_plan_capture arms the CALLING THREAD only) and
  *     (b) the optional RCCL communicator created / destroyed explicitly by hgr_comm_init / hgr_comm_destroy and
      (c) the 16-slot scratch ring of hgr_sumsq (see there);
  *   - returns 0 on success, a negative HGR_E* code otherwise; hgr_last_error() returns the message of
@@ -30,8 +31,8 @@ extern "C" {
 #endif
 
 /* 2: round-2 additions (LayerNorm-folded GEMMs, hgr_logits_eval, RCCL collectives, the training-step fusions); 4: round-4 additions
- * (hgr_gemm_nt_ln_mha); every earlier entry point is unchanged */
-#define HGR_ABI_VERSION 4
+ * (hgr_gemm_nt_ln_mha); 5: hgr_gemm_plan_capture; every earlier entry point is unchanged */
+#define HGR_ABI_VERSION 5
 
 enum { HGR_OK = 0, HGR_EINVAL = -1, HGR_EUNSUPPORTED = -2, HGR_ELAUNCH = -3 };
 
@@ -341,6 +342,24 @@ int hgr_gemm_tn_splitk(const void *P, int64_t ldp, const void *Q, int64_t ldq, f
  * kc for ~256 workgroups per round), 128 x 128 tiles run two per CU (~512).  Pure function of the shape (HGR_TN_TILE=128|256
  * in the environment pins it, for A/B runs); not an error code. */
 int hgr_gemm_tn_tile(int Na, int Nb);
+
+/* The same for the NT family: which kernel, tile plan and grid a call gets, as a function of its arguments and the knobs above.
+ * hgr_gemm_plan_capture arms capture for the CALLING THREAD: the next call of hgr_gemm_nt, hgr_gemm_nt_splitk, hgr_conv3x3_nhwc[_plain],
+ * hgr_gemm_nt_res_stats[_guard], hgr_gemm_nt_ln, hgr_gemm_nt_bias_gelu_dual or hgr_gemm_nt_qgelu_grad_colsum on that thread validates
+ * and plans as usual, writes the launches it would make into out[0 .. max_launches) (zero-filled by the caller; kernel = 0 ends the
+ * list; a call makes at most two), launches NOTHING, returns HGR_OK and disarms; a call that fails validation disarms too.
+ * hgr_gemm_plan_capture(NULL, 0) disarms without a call and returns 1 if the thread was still armed, 0 if not.  Host
+ * only - the operands are never dereferenced, so tests replay shapes without a device (tests/golden/gemm_plans.json).
+ *   kernel   HGR_KERNEL_*;  variant: gemm_nt_128 0 plain / 1 tall 256 x 64 / 2 conv / 3 conv tall; gemm_nt_256 1 = conv; gemm_nt_duo
+ *            0 plain / 1 residual producer / 2 LayerNorm consumer / 4 dual output / 5 conv; gemm_nt_ws 0 plain / 1 consumer / 2 producer;
+ *            conv-direct: the input channels
+ *   epilogue, out_f32, act   the instantiation (act: QuickGELU 1 / ReLU 2 of gemm_nt_ws and gemm_nt_p8, relu of conv-direct)
+ *   grid_x, grid_y           the launch grid (0 for conv-direct, which sizes its own)
+ *   tiles_m .. vec_ok        the plan as the kernel receives it;  row0, rows: the rows of A / C the launch covers */
+enum { HGR_KERNEL_128 = 1, HGR_KERNEL_256 = 2, HGR_KERNEL_DUO = 3, HGR_KERNEL_WS = 4, HGR_KERNEL_P8 = 5, HGR_KERNEL_CONV_DIRECT = 6 };
+typedef struct { int32_t kernel, variant, epilogue, out_f32, act, grid_x, grid_y, tiles_m, tiles_n, total,
+                 nbig, big_panels, tiles_m_half, group, m_fastest, vec_ok, row0, rows; } hgr_gemm_launch;
+int hgr_gemm_plan_capture(hgr_gemm_launch *out, int max_launches);
 
 /* The same for a 3x3 / pad 1 / stride 1 convolution (every 3x3 of clip/model.py's Bottleneck and stem conv2/conv3):
  *   partial[s][co][(ky, kx, c)] = sum over pixels m of slice s of dY[m][co] * x[pixel m shifted by (ky-1, kx-1)][c]

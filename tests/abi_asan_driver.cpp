@@ -107,6 +107,19 @@ int main() {
     EXPECT_FAIL(hgr_layernorm_bwd_cast_colsum(h16, 0, f32, f32, f32, h16, f32, f32, nullptr, f32, 4, 64, 1, nullptr, 1e-5f, HGR_F16, nullptr));
     EXPECT_FAIL(hgr_layernorm_bwd_cast(h16, 0, f32, f32, f32, h16, f32, f32, f32, 4, 6, 1, nullptr, 1e-5f, HGR_F16, nullptr));         // W % 4
     EXPECT_OK(hgr_gemm_tn_tile(3072, 768) == 256 && hgr_gemm_tn_tile(200, 4096) == 128 && hgr_gemm_tn_tile(640, 640) == 128 ? 0 : -1);
+    // plan capture: a captured call validates, plans, launches nothing and disarms; a rejected call disarms too
+    static hgr_gemm_launch plan[4];
+    EXPECT_FAIL(hgr_gemm_plan_capture(nullptr, 4));
+    EXPECT_FAIL(hgr_gemm_plan_capture(plan, 0));
+    EXPECT_OK(hgr_gemm_plan_capture(plan, 4));
+    EXPECT_OK(hgr_gemm_nt(h16, 768, h16, 768, h16, 768, f32, nullptr, 0, 25600, 768, 768, HGR_F16, HGR_EPI_BIAS, 0, nullptr));
+    EXPECT_OK(plan[0].kernel == HGR_KERNEL_DUO && plan[0].rows == 25600 && plan[0].grid_x > 0 && plan[1].kernel == 0 ? 0 : -1);
+    EXPECT_OK(hgr_gemm_plan_capture(plan, 4));
+    EXPECT_FAIL(hgr_gemm_nt(nullptr, 768, h16, 768, h16, 768, f32, nullptr, 0, 25600, 768, 768, HGR_F16, HGR_EPI_BIAS, 0, nullptr));
+    EXPECT_OK(hgr_gemm_plan_capture(nullptr, 0) == 0 ? 0 : -1);                                                                          // the rejected call disarmed
+    EXPECT_OK(hgr_gemm_plan_capture(plan, 4));
+    EXPECT_OK(hgr_gemm_plan_capture(nullptr, 0) == 1 ? 0 : -1);                                                                          // still armed: disarms
+    EXPECT_OK(hgr_gemm_plan_capture(nullptr, 0) == 0 ? 0 : -1);
     // collectives without a communicator / with bad arguments (librccl may be absent: both outcomes are failures by contract)
     EXPECT_FAIL(hgr_allreduce(f32, f32, 16, HGR_COMM_F32, HGR_COMM_SUM, nullptr));
     EXPECT_FAIL(hgr_allgather(f32, f32, 16, 99, nullptr));

@@ -25,7 +25,55 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"libhgr.so does not export {name}"
     assert declared - {"hgr_abi_version", "hgr_last_error"} == set(_lib.SIGNATURES), "ctypes table out of sync with hgr.h"
-    assert lib.hgr_abi_version() == _lib.ABI_VERSION == 4
+    assert lib.hgr_abi_version() == _lib.ABI_VERSION == 5
+
+
+def test_gemm_plans_match_golden(tmp_path, golden_dir):
+    """Which kernel, tile plan and grid every route of the NT GEMM family takes (hgr_gemm_plan_capture: validated and planned, nothing
+    launched, no device needed) against tests/golden/gemm_plans.json.  The table was recorded from the host code BEFORE the plan step
+    existed - a scratch build of that commit with a tagged print in front of every launch_* call of hgr_gemm.hip and of the post-adjustment
+    grid / total inside launch_duo, launch_ws and launch_p8, run on a machine without a GPU (256 CUs assumed, as on an MI355X) - so it
+    pins the routes the GPU parity tests name in their docstrings: the shapes of test_gemm_tail_plan_is_bit_identical,
+    test_gemm_res_stats_persistent_is_bit_identical, test_gemm_ws_equals_duo and test_gemm_p8_equals_duo under their switches, the
+    ViT-B/32 batch-512 tower launches, the corners of the tail plan and of the cost model, split-K and every branch of the convolution
+    ladder.  A changed threshold shows up here instead of silently moving a parity test off the path it was written for.  The library
+    reads its environment once, so every environment of the table gets a fresh process, one after another, started without HGR_*
+    variables of the caller and with the device hidden: the plan is then the 256-CU one the table holds on any machine, and no
+    child opens the GPU."""
+    from hgr_net_amd import _lib, ops
+    sys.path.insert(0, str(ROOT / "tests" / "workers"))
+    try:
+        import gemm_plan_replay as replay
+    finally:
+        sys.path.pop(0)
+    assert all(_lib.SIGNATURES[name] == argtypes for name, argtypes in replay.ARGTYPES.items())
+    rows = json.loads((golden_dir / "gemm_plans.json").read_text())
+    assert 100 < len(rows) < 500 and all(row["launches"] for row in rows)
+    got = [None] * len(rows)
+    by_env = {}
+    for i, row in enumerate(rows):
+        by_env.setdefault(json.dumps(row["env"], sort_keys=True), []).append(i)
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("HGR_")}
+    for n, (key, idx) in enumerate(by_env.items()):
+        (tmp_path / f"rows{n}.json").write_text(json.dumps([rows[i] for i in idx]))
+        child = subprocess.run([sys.executable, replay.__file__, str(_lib.LIB_PATH), str(tmp_path / f"rows{n}.json")], capture_output=True, text=True, timeout=120,
+                               env=dict(clean, **json.loads(key), HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES=""))
+        assert child.returncode == 0, child.stderr[-2000:]
+        for i, launches in zip(idx, json.loads(child.stdout)):
+            got[i] = launches
+    for row, launches in zip(rows, got):
+        assert launches == row["launches"], {k: row[k] for k in ("entry", "args", "knobs", "env")}
+
+    # ops.gemm_plan is the same capture (in this process: whatever card and environment it has); it never leaves the thread armed
+    lib, row = _lib.load(), rows[0]
+    plan = ops.gemm_plan(lambda: replay.call(lib, row["entry"], row["args"]))
+    assert plan and plan == replay.replay(lib, [dict(row, knobs={})])[0]
+    with pytest.raises(ZeroDivisionError):
+        ops.gemm_plan(lambda: 1 // 0)
+    assert lib.hgr_gemm_plan_capture(None, 0) == 0
+    with pytest.raises(_lib.HgrError):
+        ops.gemm_plan(lambda: None)
+    assert lib.hgr_gemm_plan_capture(None, 0) == 0
 
 
 def test_product_library_has_no_ablation_switches():
