@@ -39,7 +39,7 @@ class Evaluator:
         had finished and exposed the next step's launch latency (0.3 ms of a 6.3 ms step at ViT-B/32, batch 512)."""
         if self._anc is None:
             m = self.model
-            keys = list(m.c2p.keys()) if isinstance(m.c2p, dict) else list(range(len(m.c2p)))
+            keys = sorted(m.c2p.keys()) if isinstance(m.c2p, dict) else list(range(len(m.c2p)))
             ptr, nodes, levels, off = {}, [], [], 0
             for t in keys:
                 path = list(m.c2p[t]) + [t]
@@ -50,7 +50,23 @@ class Evaluator:
             dev = m.train_index.device
             lv = torch.tensor(levels, dtype=torch.int64)
             self._anc = (ptr, torch.tensor(nodes, dtype=torch.int32).to(dev), lv.to(dev), lv.to(torch.int32).to(dev))
+            # the same CSR with its pointer array on the device, for batches of mixed classes (hgr_eval_counters_rows reads the
+            # path of every row's own target): int32 [n_nodes + 1]; a node absent from c2p gets an empty range = a padding row
+            n_nodes = len(m.nodes)
+            starts, off = [0] * (n_nodes + 1), 0
+            for t in range(n_nodes):
+                starts[t] = off
+                o, n = ptr.get(t, (off, 0))
+                assert n == 0 or (o == off and n <= 32), "paths are laid out in node order, at most 32 nodes long"
+                off += n
+            starts[n_nodes] = off
+            self._anc_ptr = torch.tensor(starts, dtype=torch.int32).to(dev)
         return self._anc
+
+    def _ancestor_csr(self):
+        """(anc_ptr [n_nodes + 1], anc_nodes, anc_levels) int32 on the device: the operands of hgr_eval_counters_rows."""
+        _, nodes, _, lv32 = self._ancestor_tables()
+        return self._anc_ptr, nodes, lv32
 
     def _parents(self, target: int):
         ptr, nodes, lv64, lv32 = self._ancestor_tables()
@@ -76,6 +92,22 @@ class Evaluator:
         if not want_outputs:
             return None
         return pred, lv[:, levels64]                                                 # dict_path [B, L]
+
+    @staticmethod
+    def _row_targets(targets: torch.Tensor) -> torch.Tensor:
+        return (targets if targets.dtype == torch.int64 else targets.to(torch.int64)).contiguous().view(-1)
+
+    @torch.no_grad()
+    def add_batch_rows(self, logits: torch.Tensor, targets: torch.Tensor, want_outputs: bool = False):
+        """add_batch for a batch packed from SEVERAL classes (dataset.packing): ``targets`` int64 [B] on the device names every row's
+        own class, and hgr_eval_counters_rows scores each row against that class's path (the reference's counters are row-additive,
+        main.py:139-191).  Rows with a target outside [0, n_nodes) are padding and count nothing.  Returns (pred_top20, level
+        arg-max [B, n_levels]) with ``want_outputs``; the paths differ per row, so there is no dict_path view."""
+        if hasattr(self.model, "join_tail"):
+            self.model.join_tail()
+        lv, p1, pred = ops.eval_rows(logits, self.index, max(TOPK))
+        ops.eval_counters_rows(pred, self._row_targets(targets), p1.view(-1), lv, *self._ancestor_csr(), self.acc)
+        return (pred, lv) if want_outputs else None
 
     def fused_ok(self) -> bool:
         """hgr_logits_eval needs an embedding width that is a multiple of 128 (<= 1024) and <= 32 levels."""
@@ -115,6 +147,28 @@ class Evaluator:
             return None
         return pred, lv[:, levels64]
 
+    @torch.no_grad()
+    def add_images_rows(self, imgs: torch.Tensor, targets: torch.Tensor, want_outputs: bool = False):
+        """add_images for a batch packed from SEVERAL classes: the same three routes (two-graph pipeline, single graph, logits +
+        hgr_eval_rows for a hierarchy beyond hgr_logits_eval's capacity), with hgr_eval_counters_rows in the place of
+        hgr_eval_counters.  Same counters as add_batch_rows(model(imgs), targets)."""
+        if self._plan is None:
+            self._plan = ops.LogitsEvalPlan(self.index)
+        if not self._plan.supported:
+            return self.add_batch_rows(self.model(imgs), targets, want_outputs)
+        tg = self._row_targets(targets)
+        anc_ptr, anc_nodes, anc_levels = self._ancestor_csr()
+        if not want_outputs and hasattr(self.model, "forward_eval_overlapped"):
+            tg.record_stream(self.model._pipe_state(imgs.device)["side"])       # read by the counters on the tail's stream
+            if self.model.forward_eval_overlapped(imgs, self._plan, max(TOPK), lambda lv, p1, pred: ops.eval_counters_rows(
+                    pred, tg, p1.view(-1), lv, anc_ptr, anc_nodes, anc_levels, self.acc)):
+                return None
+        if hasattr(self.model, "join_tail"):
+            self.model.join_tail()
+        lv, p1, pred = self.model.forward_eval(imgs, self._plan, max(TOPK))
+        ops.eval_counters_rows(pred, tg, p1.view(-1), lv, anc_ptr, anc_nodes, anc_levels, self.acc)
+        return (pred, lv) if want_outputs else None
+
     def counters(self, group=None) -> Dict[str, float]:
         """Read the counters (one D2H copy); with a process group, all-reduce(sum) them first."""
         if hasattr(self.model, "join_tail"):
@@ -150,7 +204,8 @@ class Evaluator:
 @torch.no_grad()
 def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, group=None, log: bool = True) -> str:
     """Drop-in for the reference's ``test(opts, model, device, splits)`` (main.py:104-222).
-    ``loader`` yields the reference's batch dicts {'img': [1,B,3,R,R], 'label': [1,B]}."""
+    ``loader`` yields the reference's batch dicts {'img': [1,B,3,R,R], 'label': [1,B]}.  With ``opts.pack_batches`` the batches are
+    repacked into full ones of ``opts.test_batch_size`` rows of mixed classes (dataset.packing.PackedBatches); same metrics."""
     print("out", opts.out_ratio)
     print("in", opts.in_ratio)
     model.eval()
@@ -172,7 +227,20 @@ def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, gr
     print("Running.", flush=True)
     ev = Evaluator(model)
     fused = ev.fused_ok() and os.environ.get("HGR_EVAL_FUSED", "1") != "0"
+    packed = bool(getattr(opts, "pack_batches", False))
+    if packed:
+        # full batches packed from several classes (dataset.packing): one input shape = one graph generation for the whole run, every
+        # row scored against its own class; the labels arrive on the device and are never read on the host
+        from .dataset.packing import PackedBatches
+        loader = PackedBatches(loader, opts.test_batch_size, device)
     for data in loader:
+        if packed:
+            imgs, targets = data["img"][0], data["label"][0]
+            if fused:
+                ev.add_images_rows(imgs, targets)
+            else:
+                ev.add_batch_rows(model(imgs, None, static_output=True), targets)
+            continue
         imgs, targets = data["img"].to(device, non_blocking=True)[0], data["label"].to(device, non_blocking=True)[0]
         target = int(data["label"][0][0])           # host copy of the label: no device sync in the loop
         if fused:                                   # the loop never looks at the logits: GEMM + evaluation in one pass, nothing [B, N] written

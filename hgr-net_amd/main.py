@@ -75,6 +75,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--train_dtype", default="bf16", type=str)
     p.add_argument("--split_file", default=None, type=str, help="class -> image paths JSON (default data/{split}_split.json)")
     p.add_argument("--data_seed", default=None, type=int, help="seed of the loaders' class / image order (all ranks must agree)")
+    p.add_argument("--pack_batches", type=eval, default=False, choices=[True, False],
+                   help="evaluation: repack the one-class batches into full batches of mixed classes (one input shape, one set of HIP graphs)")
     p.add_argument("--ref_quirks", default=False, action="store_true",
                    help="reproduce the reference's missing zero_grad() (gradients accumulate across steps, SURVEY F11-i)")
     return p

@@ -548,6 +548,20 @@ def eval_counters(pred: torch.Tensor, targets: Optional[torch.Tensor], target: i
               _dev(levels), parents.numel(), _dev(acc), pred.shape[0], _stream())
 
 
+def eval_counters_rows(pred: torch.Tensor, targets: torch.Tensor, top1: torch.Tensor, lv: torch.Tensor, anc_ptr: torch.Tensor,
+                       anc_nodes: torch.Tensor, anc_levels: torch.Tensor, acc: torch.Tensor) -> None:
+    """Advance the nine float64 evaluation counters with one batch of MIXED classes (main.py:139-191): every row is scored against
+    the path of its own target (CSR anc_ptr [n_nodes + 1] / anc_nodes / anc_levels); rows with a target outside [0, n_nodes) are
+    padding and count nothing.  The result does not depend on the order of the rows."""
+    assert pred.dtype == top1.dtype == lv.dtype == anc_ptr.dtype == anc_nodes.dtype == anc_levels.dtype == torch.int32 and acc.dtype == torch.float64
+    assert pred.is_contiguous() and lv.is_contiguous() and top1.is_contiguous() and acc.numel() == 9
+    assert anc_ptr.is_contiguous() and anc_nodes.is_contiguous() and anc_levels.is_contiguous() and anc_ptr.numel() >= 2
+    assert targets is not None and targets.dtype == torch.int64 and targets.is_contiguous() and targets.numel() == pred.shape[0]
+    assert top1.numel() == pred.shape[0] and lv.shape[0] == pred.shape[0]
+    _lib.call("hgr_eval_counters_rows", _dev(pred), pred.shape[1], _dev(targets), _dev(top1), _dev(lv), lv.shape[1], _dev(anc_ptr),
+              _dev(anc_nodes), _dev(anc_levels), anc_ptr.numel() - 1, _dev(acc), pred.shape[0], _stream())
+
+
 # ---- ModifiedResNet (RN) tower -------------------------------------------------------------------
 def conv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, b: int, h: int, wd: int, c: int,
                  stride: int = 1) -> torch.Tensor:

@@ -262,6 +262,18 @@ int hgr_eval_rows(const float *logits, int64_t ld, int n_nodes, const unsigned c
 int hgr_eval_counters(const int32_t *pred, int k, const int64_t *targets, int target, const int32_t *top1, const int32_t *lv,
                       int n_levels, const int32_t *parents, const int32_t *levels, int L, double *acc, int rows, void *stream);
 
+/* The same counters (main.py:139-191) for a batch packed from SEVERAL classes: every row is scored against the path of its own
+ * target.  targets int64 [rows], required; a row with targets[r] < 0 or >= n_nodes is padding: skipped, nothing counted (acc[8]
+ * included), no table read.  anc_ptr int32 [n_nodes + 1], anc_nodes / anc_levels int32: the CSR of every node's path (ancestors
+ * + itself, main.py:163) and the depth of each node on it (main.py:164); path length L = anc_ptr[t + 1] - anc_ptr[t] in 1..32,
+ * an empty range counts as padding.  The reference's counters are row-additive: hits count rows, path_all adds edge / (L - 1)
+ * (the first level's match when L == 1, main.py:179-180), point_all adds point / L.  Integer counts, edge and point binned by L,
+ * finalised by one thread in a fixed order: acc does not depend on the order of the rows.  One block, rows strided over it;
+ * k <= 32, n_levels <= 32. */
+int hgr_eval_counters_rows(const int32_t *pred, int k, const int64_t *targets, const int32_t *top1, const int32_t *lv, int n_levels,
+                           const int32_t *anc_ptr, const int32_t *anc_nodes, const int32_t *anc_levels, int n_nodes,
+                           double *acc, int rows, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * ModifiedResNet (RN50) tower, clip/model.py:93-150.  Activations are NHWC 16-bit ([B, H, W, C] =
  * a row-major [B*H*W, C] matrix), so every 1x1 convolution IS hgr_gemm_nt; inference BatchNorm
