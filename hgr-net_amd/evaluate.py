@@ -10,6 +10,7 @@ Outputs (counter values and the printed string) are identical to the reference's
 """
 from __future__ import annotations
 
+import json
 import os
 from typing import Dict, Iterable, Optional
 
@@ -23,10 +24,12 @@ COUNTERS = ["hits@1", "hits@2", "hits@5", "hits@10", "hits@20", "hits_all", "pat
 
 
 class Evaluator:
-    def __init__(self, model):
+    def __init__(self, model, report: bool = False):
         self.model = model
         dev = model.train_index.device
         self.acc = torch.zeros(len(COUNTERS), dtype=torch.float64, device=dev)
+        # the hierarchy report (hgr_eval_report_rows): an int64 table advanced beside the counters, or None = nothing extra is launched
+        self.report = torch.zeros(ops.REPORT_LEN, dtype=torch.int64, device=dev) if report else None
         self.n_levels = model.max_depth + 1
         self.index = ops.EvalIndex(model.depth32, model.train_index32, model.test_index32, self.n_levels)   # dense per-column maps, built once
         self._anc = None         # ancestor paths of every node as a device CSR (see _ancestor_tables)
@@ -89,6 +92,8 @@ class Evaluator:
             tg = targets if targets.dtype == torch.int64 else targets.to(torch.int64)
             tg = tg.contiguous()
         ops.eval_counters(pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)
+        if self.report is not None:
+            self._report(pred, self._class_targets(tg, target, pred), p1, lv)
         if not want_outputs:
             return None
         return pred, lv[:, levels64]                                                 # dict_path [B, L]
@@ -96,6 +101,17 @@ class Evaluator:
     @staticmethod
     def _row_targets(targets: torch.Tensor) -> torch.Tensor:
         return (targets if targets.dtype == torch.int64 else targets.to(torch.int64)).contiguous().view(-1)
+
+    @staticmethod
+    def _class_targets(tg: Optional[torch.Tensor], target: int, like: torch.Tensor) -> torch.Tensor:
+        """The row targets of a single-class batch for the report: the ones given, else ``target`` for every row of ``like``."""
+        if tg is not None:
+            return tg.view(-1)
+        return torch.full((like.shape[0],), int(target), dtype=torch.int64, device=like.device)
+
+    def _report(self, pred, tg, p1, lv) -> None:
+        """One hgr_eval_report_rows launch on the current stream, on the outputs the counters were just advanced with."""
+        ops.eval_report_rows(pred, tg, p1.view(-1), lv, *self._ancestor_csr(), self.report)
 
     @torch.no_grad()
     def add_batch_rows(self, logits: torch.Tensor, targets: torch.Tensor, want_outputs: bool = False):
@@ -106,7 +122,10 @@ class Evaluator:
         if hasattr(self.model, "join_tail"):
             self.model.join_tail()
         lv, p1, pred = ops.eval_rows(logits, self.index, max(TOPK))
-        ops.eval_counters_rows(pred, self._row_targets(targets), p1.view(-1), lv, *self._ancestor_csr(), self.acc)
+        tg = self._row_targets(targets)
+        ops.eval_counters_rows(pred, tg, p1.view(-1), lv, *self._ancestor_csr(), self.acc)
+        if self.report is not None:
+            self._report(pred, tg, p1, lv)
         return (pred, lv) if want_outputs else None
 
     def fused_ok(self) -> bool:
@@ -134,15 +153,27 @@ class Evaluator:
         if not want_outputs and hasattr(self.model, "forward_eval_overlapped"):
             # the loop's own route: the step as a two-stage pipeline (the class-token tail of this batch beside the next batch's tower);
             # the counters are advanced on the tail's stream, counters() / summary() join it
+            side = self.model._pipe_state(imgs.device)["side"]
             if tg is not None:
-                tg.record_stream(self.model._pipe_state(imgs.device)["side"])
-            if self.model.forward_eval_overlapped(imgs, self._plan, max(TOPK), lambda lv, p1, pred: ops.eval_counters(
-                    pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)):
+                tg.record_stream(side)
+            rt = None
+            if self.report is not None:
+                rt = self._class_targets(tg, target, imgs)   # made on this stream, ahead of the head: ordered before the tail reads it
+                rt.record_stream(side)
+                self._ancestor_csr()                          # uploaded (first use) on this stream, not on the tail's
+
+            def consume(lv, p1, pred):                        # on the tail's stream: the report directly behind the counters
+                ops.eval_counters(pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)
+                if rt is not None:
+                    self._report(pred, rt, p1, lv)
+            if self.model.forward_eval_overlapped(imgs, self._plan, max(TOPK), consume):
                 return None
         if hasattr(self.model, "join_tail"):
             self.model.join_tail()                      # the counters may still be in flight on the tail stream of earlier batches
         lv, p1, pred = self.model.forward_eval(imgs, self._plan, max(TOPK))
         ops.eval_counters(pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)
+        if self.report is not None:
+            self._report(pred, self._class_targets(tg, target, pred), p1, lv)
         if not want_outputs:
             return None
         return pred, lv[:, levels64]
@@ -160,13 +191,19 @@ class Evaluator:
         anc_ptr, anc_nodes, anc_levels = self._ancestor_csr()
         if not want_outputs and hasattr(self.model, "forward_eval_overlapped"):
             tg.record_stream(self.model._pipe_state(imgs.device)["side"])       # read by the counters on the tail's stream
-            if self.model.forward_eval_overlapped(imgs, self._plan, max(TOPK), lambda lv, p1, pred: ops.eval_counters_rows(
-                    pred, tg, p1.view(-1), lv, anc_ptr, anc_nodes, anc_levels, self.acc)):
+
+            def consume(lv, p1, pred):                        # on the tail's stream: the report directly behind the counters
+                ops.eval_counters_rows(pred, tg, p1.view(-1), lv, anc_ptr, anc_nodes, anc_levels, self.acc)
+                if self.report is not None:
+                    self._report(pred, tg, p1, lv)
+            if self.model.forward_eval_overlapped(imgs, self._plan, max(TOPK), consume):
                 return None
         if hasattr(self.model, "join_tail"):
             self.model.join_tail()
         lv, p1, pred = self.model.forward_eval(imgs, self._plan, max(TOPK))
         ops.eval_counters_rows(pred, tg, p1.view(-1), lv, anc_ptr, anc_nodes, anc_levels, self.acc)
+        if self.report is not None:
+            self._report(pred, tg, p1, lv)
         return (pred, lv) if want_outputs else None
 
     def counters(self, group=None) -> Dict[str, float]:
@@ -200,6 +237,87 @@ class Evaluator:
         out += " point_ratio(%):{:.2f}".format(c["point_all"] / n * 100.0)
         return out
 
+    def report_table(self, group=None) -> torch.Tensor:
+        """The hierarchy report's table as a CPU int64 tensor [ops.REPORT_LEN] (one D2H copy); with a process group the tables of
+        all ranks are summed first - an int64 all-reduce, exact, on the device (nccl) as on CPU tensors (gloo)."""
+        assert self.report is not None, "Evaluator(model, report=True) keeps the hierarchy report"
+        if hasattr(self.model, "join_tail"):
+            self.model.join_tail()                      # pipelined steps advance the table on the tail stream
+        table = self.report
+        if group is not None:
+            import torch.distributed as dist
+            table = table.clone()
+            dist.all_reduce(table, op=dist.ReduceOp.SUM, group=group)
+        return table.cpu()
+
+    def report_dict(self, group=None) -> dict:
+        """The hierarchy report as plain Python values (report_from_table), ready for json.dump."""
+        return report_from_table(self.report_table(group), k=max(TOPK))
+
+
+def _mistakes(hist) -> dict:
+    """One distance histogram [ops.REPORT_DIST_BINS] -> counts, the rows without a distance ("unknown": the prediction has no path
+    of 1..32 nodes) and the mean tree distance over the rows that have one and over the wrong ones among them (None without any)."""
+    known = hist[:ops.REPORT_DIST_UNKNOWN]
+    n, total = sum(known), sum(d * c for d, c in enumerate(known))
+    wrong = n - known[0]
+    return {"histogram": {str(d): c for d, c in enumerate(known) if c}, "unknown": hist[ops.REPORT_DIST_UNKNOWN],
+            "mean_distance": total / n if n else None, "mean_distance_wrong": total / wrong if wrong else None}
+
+
+def report_from_table(table: torch.Tensor, k: int = max(TOPK)) -> dict:
+    """The table of hgr_eval_report_rows (CPU int64 [ops.REPORT_LEN], layout in include/hgr.h) as plain Python values; a pure
+    function of the table.  Depths (= path length - 1) and levels without rows are left out.  The ratios are those of
+    Evaluator.summary() restricted to a depth: hits / rows, anc_hit / rows, edge / (L - 1) / rows (edge / rows at L = 1),
+    point / L / rows, all in percent.  ``k`` = the number of predictions per row the table was counted with (height_at_k averages
+    over min(K, k) predictions)."""
+    assert table.dtype == torch.int64 and table.numel() == ops.REPORT_LEN and not table.is_cuda
+    t = table.view(-1).tolist()
+    cols = ops.REPORT_DEPTH_COLS
+    by_depth, num_sample = [], 0
+    for L in range(1, ops.REPORT_MAXL + 1):
+        row = dict(zip(cols, t[ops.REPORT_DEPTH + L * len(cols):ops.REPORT_DEPTH + (L + 1) * len(cols)]))
+        n = row["rows"]
+        if n == 0:
+            continue
+        num_sample += n
+        e = {"depth": L - 1, "rows": n}
+        for kk in TOPK:
+            e[f"hits@{kk}"] = row[f"hit@{kk}"]
+            e[f"acc@{kk}"] = row[f"hit@{kk}"] / n * 100.0
+        e["hit_ratio"] = row["anc_hit"] / n * 100.0
+        e["path_ratio"] = row["edge"] / max(L - 1, 1) / n * 100.0
+        e["point_ratio"] = row["point"] / L / n * 100.0
+        e["chain_ratio"] = row["chain"] / n * 100.0
+        by_depth.append(e)
+    by_level = []
+    for i in range(ops.REPORT_MAXL):
+        n, m = t[ops.REPORT_LEVEL + 2 * i], t[ops.REPORT_LEVEL + 2 * i + 1]
+        if n:
+            by_level.append({"level": i, "rows": n, "matches": m, "accuracy": m / n * 100.0})
+    height = {}
+    for i, kk in enumerate(ops.REPORT_HEIGHT_K):
+        h = t[ops.REPORT_HEIGHT + i]
+        height[str(kk)] = {"sum": h, "per_row": h / num_sample if num_sample else None,
+                           "per_prediction": h / (num_sample * min(kk, k)) if num_sample else None}
+    return {"num_sample": num_sample, "by_depth": by_depth, "by_level": by_level,
+            "mistakes": {"test_top1": _mistakes(t[ops.REPORT_DIST_TEST:ops.REPORT_DIST_TEST + ops.REPORT_DIST_BINS]),
+                         "all_top1": _mistakes(t[ops.REPORT_DIST_ALL:ops.REPORT_DIST_ALL + ops.REPORT_DIST_BINS])},
+            "height_at_k": height}
+
+
+def format_report(rep: dict) -> str:
+    """The short per-depth table evaluate.test prints beside the report file."""
+    lines = ["depth     rows  acc@1(%)  acc@5(%)  hit(%)  path(%)  point(%)  chain(%)"]
+    for e in rep["by_depth"]:
+        lines.append("{:5d} {:8d}  {:8.2f}  {:8.2f}  {:6.2f}  {:7.2f}  {:8.2f}  {:8.2f}".format(
+            e["depth"], e["rows"], e["acc@1"], e["acc@5"], e["hit_ratio"], e["path_ratio"], e["point_ratio"], e["chain_ratio"]))
+    for name in ("test_top1", "all_top1"):
+        m = rep["mistakes"][name]
+        if m["mean_distance_wrong"] is not None:
+            lines.append("{}: mean tree distance of a wrong prediction {:.2f} ({} without a path)".format(name, m["mean_distance_wrong"], m["unknown"]))
+    return "\n".join(lines)
+
 
 @torch.no_grad()
 def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, group=None, log: bool = True) -> str:
@@ -225,7 +343,8 @@ def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, gr
                                       workers=getattr(opts, "num_workers", 8))
         print("number of batches:{}".format(loader.batch_sampler.num_batch))
     print("Running.", flush=True)
-    ev = Evaluator(model)
+    report_path = getattr(opts, "hier_report", None)
+    ev = Evaluator(model, report=True) if report_path else Evaluator(model)
     fused = ev.fused_ok() and os.environ.get("HGR_EVAL_FUSED", "1") != "0"
     packed = bool(getattr(opts, "pack_batches", False))
     if packed:
@@ -251,6 +370,13 @@ def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, gr
     print("End of testing.")
     out = ev.summary(group)
     print(out, flush=True)
+    if report_path:                                      # every rank joins the all-reduce, rank 0 writes
+        rep = ev.report_dict(group)
+        import torch.distributed as dist
+        if group is None or dist.get_rank() == 0:
+            with open(report_path, "w") as f:
+                json.dump(rep, f, indent=1)
+            print(format_report(rep), flush=True)
     if log:
         with open(model.save_path + "arugements.log", "a") as f:
             f.writelines(out + "\n")

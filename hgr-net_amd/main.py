@@ -77,6 +77,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--data_seed", default=None, type=int, help="seed of the loaders' class / image order (all ranks must agree)")
     p.add_argument("--pack_batches", type=eval, default=False, choices=[True, False],
                    help="evaluation: repack the one-class batches into full batches of mixed classes (one input shape, one set of HIP graphs)")
+    p.add_argument("--hier_report", default=None, type=str, metavar="PATH",
+                   help="evaluation: also count per depth, per path level and by tree distance of the mistakes (hgr_eval_report_rows) and "
+                        "write the report as JSON to PATH")
     p.add_argument("--ref_quirks", default=False, action="store_true",
                    help="reproduce the reference's missing zero_grad() (gradients accumulate across steps, SURVEY F11-i)")
     return p

@@ -562,6 +562,35 @@ def eval_counters_rows(pred: torch.Tensor, targets: torch.Tensor, top1: torch.Te
               _dev(anc_nodes), _dev(anc_levels), anc_ptr.numel() - 1, _dev(acc), pred.shape[0], _stream())
 
 
+# layout of the hierarchy report's table: mirrors HGR_REPORT_* of include/hgr.h (offsets in int64 entries)
+REPORT_MAXL = 32
+REPORT_DEPTH_COLS = ("rows", "hit@1", "hit@2", "hit@5", "hit@10", "hit@20", "anc_hit", "point", "edge", "chain")
+REPORT_DEPTH = 0                                                   # [33][10] by the target's path length L
+REPORT_LEVEL = REPORT_DEPTH + (REPORT_MAXL + 1) * len(REPORT_DEPTH_COLS)      # [32][2] by path position: rows, matches
+REPORT_DIST_BINS = 2 * REPORT_MAXL + 2                             # distances 0..64 and "unknown"
+REPORT_DIST_UNKNOWN = 2 * REPORT_MAXL + 1
+REPORT_DIST_TEST = REPORT_LEVEL + 2 * REPORT_MAXL                  # [66] dist(pred[r, 0], target)
+REPORT_DIST_ALL = REPORT_DIST_TEST + REPORT_DIST_BINS              # [66] dist(top1[r], target)
+REPORT_HEIGHT = REPORT_DIST_ALL + REPORT_DIST_BINS                 # [5] summed heights of the first K predictions, K in REPORT_HEIGHT_K
+REPORT_HEIGHT_K = (1, 2, 5, 10, 20)
+REPORT_LEN = REPORT_HEIGHT + len(REPORT_HEIGHT_K)                  # 531
+
+
+def eval_report_rows(pred: torch.Tensor, targets: torch.Tensor, top1: torch.Tensor, lv: torch.Tensor, anc_ptr: torch.Tensor,
+                     anc_nodes: torch.Tensor, anc_levels: torch.Tensor, table: torch.Tensor) -> None:
+    """Add one batch to the hierarchy report's int64 table (layout above; definitions in include/hgr.h): the operands of
+    eval_counters_rows, the same padding rule, exact integer counts only - the table does not depend on the order of the rows or on
+    how they were cut into calls."""
+    assert pred.dtype == top1.dtype == lv.dtype == anc_ptr.dtype == anc_nodes.dtype == anc_levels.dtype == torch.int32
+    assert table.dtype == torch.int64 and table.numel() == REPORT_LEN and table.is_contiguous()
+    assert pred.is_contiguous() and lv.is_contiguous() and top1.is_contiguous()
+    assert anc_ptr.is_contiguous() and anc_nodes.is_contiguous() and anc_levels.is_contiguous() and anc_ptr.numel() >= 2
+    assert targets is not None and targets.dtype == torch.int64 and targets.is_contiguous() and targets.numel() == pred.shape[0]
+    assert top1.numel() == pred.shape[0] and lv.shape[0] == pred.shape[0]
+    _lib.call("hgr_eval_report_rows", _dev(pred), pred.shape[1], _dev(targets), _dev(top1), _dev(lv), lv.shape[1], _dev(anc_ptr),
+              _dev(anc_nodes), _dev(anc_levels), anc_ptr.numel() - 1, _dev(table), pred.shape[0], _stream())
+
+
 # ---- ModifiedResNet (RN) tower -------------------------------------------------------------------
 def conv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, b: int, h: int, wd: int, c: int,
                  stride: int = 1) -> torch.Tensor:

@@ -274,6 +274,42 @@ int hgr_eval_counters_rows(const int32_t *pred, int k, const int64_t *targets, c
                            const int32_t *anc_ptr, const int32_t *anc_nodes, const int32_t *anc_levels, int n_nodes,
                            double *acc, int rows, void *stream);
 
+/* The hierarchy report: what main.py:139-191 sums over every class and depth, kept apart by the depth of the target, by the level
+ * of the path and by how far in the tree a wrong prediction lies.  Same operands as hgr_eval_counters_rows, an int64 table
+ * [HGR_REPORT_LEN] on the device in the place of acc; the kernel only ever ADDS exact integer counts (64-bit atomics), so the table
+ * after any sequence of launches depends neither on the order of the rows nor on how they were cut into launches.  A row is padding
+ * (counts nothing) exactly when it is padding for hgr_eval_counters_rows: target outside [0, n_nodes) or path length outside 1..32.
+ *   P(x) = anc_nodes[anc_ptr[x] : anc_ptr[x + 1]] (ancestors from the top down, then x), Lx its length; t = the row's target
+ *   c(x, t)      = length of the longest common PREFIX of P(x) and P(t) (leading equal positions only)
+ *   height(x, t) = Lt - c      dist(x, t) = Lx + Lt - 2 c  (0..64, 0 exactly when x == t)
+ *   a prediction outside [0, n_nodes) or with Lx outside 1..32 is "unknown": bin HGR_REPORT_DIST_UNKNOWN, height Lt
+ *   parent(x)    = P(x)[Lx - 2] if Lx >= 2, else "root"
+ * Layout (offsets in int64 entries):
+ *   HGR_REPORT_DEPTH  [33][10]  by the target's path length L (row 0 stays zero): rows, hit@1, @2, @5, @10, @20 (first match of t
+ *                               in pred[r, :k]), anc_hit (path nodes equal to top1[r]), point (positions i with lv[r, level of
+ *                               P(t)[i]] == P(t)[i]), edge (consecutive matched pairs; the single match when L == 1), chain (1 if
+ *                               the picks q_i = lv[r, level of P(t)[i]] are all node ids, parent(q_0) is "root" and
+ *                               parent(q_{i+1}) == q_i for every i)
+ *   HGR_REPORT_LEVEL  [32][2]   by path position i: rows with L > i, rows among them matched at position i
+ *   HGR_REPORT_DIST_TEST [66]   histogram of dist(pred[r, 0], t); HGR_REPORT_DIST_ALL [66] the same for top1[r]
+ *   HGR_REPORT_HEIGHT [5]       K in (1, 2, 5, 10, 20): sum over rows of the heights of pred[r, i], i < min(K, k)
+ * One wave per row, a fixed grid of at most 8 blocks, per-launch counts in LDS, one flush per block; k <= 32, n_levels <= 32. */
+#define HGR_REPORT_MAXL 32
+#define HGR_REPORT_DEPTH_COLS 10
+enum { HGR_REPORT_COL_ROWS = 0, HGR_REPORT_COL_HIT1 = 1, HGR_REPORT_COL_HIT2 = 2, HGR_REPORT_COL_HIT5 = 3, HGR_REPORT_COL_HIT10 = 4,
+       HGR_REPORT_COL_HIT20 = 5, HGR_REPORT_COL_ANC_HIT = 6, HGR_REPORT_COL_POINT = 7, HGR_REPORT_COL_EDGE = 8, HGR_REPORT_COL_CHAIN = 9 };
+#define HGR_REPORT_DEPTH 0
+#define HGR_REPORT_LEVEL (HGR_REPORT_DEPTH + (HGR_REPORT_MAXL + 1) * HGR_REPORT_DEPTH_COLS)      /* 330 */
+#define HGR_REPORT_DIST_BINS (2 * HGR_REPORT_MAXL + 2)                                            /* 0..64 and "unknown" */
+#define HGR_REPORT_DIST_UNKNOWN (2 * HGR_REPORT_MAXL + 1)
+#define HGR_REPORT_DIST_TEST (HGR_REPORT_LEVEL + 2 * HGR_REPORT_MAXL)                             /* 394 */
+#define HGR_REPORT_DIST_ALL (HGR_REPORT_DIST_TEST + HGR_REPORT_DIST_BINS)                         /* 460 */
+#define HGR_REPORT_HEIGHT (HGR_REPORT_DIST_ALL + HGR_REPORT_DIST_BINS)                            /* 526 */
+#define HGR_REPORT_LEN (HGR_REPORT_HEIGHT + 5)                                                    /* 531 */
+int hgr_eval_report_rows(const int32_t *pred, int k, const int64_t *targets, const int32_t *top1, const int32_t *lv, int n_levels,
+                         const int32_t *anc_ptr, const int32_t *anc_nodes, const int32_t *anc_levels, int n_nodes, int64_t *table,
+                         int rows, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * ModifiedResNet (RN50) tower, clip/model.py:93-150.  Activations are NHWC 16-bit ([B, H, W, C] =
  * a row-major [B*H*W, C] matrix), so every 1x1 convolution IS hgr_gemm_nt; inference BatchNorm
