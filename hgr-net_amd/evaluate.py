@@ -76,6 +76,76 @@ class Evaluator:
         o, n = ptr[target]
         return nodes[o:o + n], lv64[o:o + n], lv32[o:o + n], n
 
+    # ---- scoring: two scorers x three routes -----------------------------------------------------------------------------------------
+    # A scorer is (score(lv, p1, pred), [tensors score reads that this batch made], view(lv)): score advances the counters and, directly
+    # behind them on the same stream, the report (if kept); view gives the level output the caller gets back.  Scorers are built on the
+    # CALLER's stream before anything of the step is launched: whatever they make there (converted targets, the report's row targets,
+    # the first upload of the ancestor CSR) is ordered ahead of the head, hence ahead of the tail that reads it.
+    @staticmethod
+    def _row_targets(targets: torch.Tensor) -> torch.Tensor:
+        return (targets if targets.dtype == torch.int64 else targets.to(torch.int64)).contiguous().view(-1)
+
+    def _class_scorer(self, target: int, targets: Optional[torch.Tensor], like: torch.Tensor):
+        """One class for every row of the batch ``like`` (hgr_eval_counters); ``targets``: the same class per row, if the caller has it."""
+        parents, levels64, levels32, _ = self._parents(target)
+        tg = None if targets is None else self._row_targets(targets)
+        rt = csr = None
+        if self.report is not None:                  # the report scores rows: without targets, ``target`` for every row
+            rt = tg if tg is not None else torch.full((like.shape[0],), int(target), dtype=torch.int64, device=like.device)
+            csr = self._ancestor_csr()
+
+        def score(lv, p1, pred):
+            ops.eval_counters(pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)
+            if rt is not None:
+                ops.eval_report_rows(pred, rt, p1.view(-1), lv, *csr, self.report)
+        return score, [t for t in (tg, rt) if t is not None], lambda lv: lv[:, levels64]        # dict_path [B, L]
+
+    def _rows_scorer(self, targets: torch.Tensor):
+        """Every row against the path of its own class (hgr_eval_counters_rows); the paths differ per row, so there is no dict_path view."""
+        tg = self._row_targets(targets)
+        csr = self._ancestor_csr()
+
+        def score(lv, p1, pred):
+            ops.eval_counters_rows(pred, tg, p1.view(-1), lv, *csr, self.acc)
+            if self.report is not None:
+                ops.eval_report_rows(pred, tg, p1.view(-1), lv, *csr, self.report)
+        return score, [tg], lambda lv: lv
+
+    def _join_tail(self) -> None:
+        """Counters and report may still be in flight on the tail stream of earlier pipelined batches: order this stream behind them."""
+        if hasattr(self.model, "join_tail"):
+            self.model.join_tail()
+
+    def _fused_plan(self) -> "ops.LogitsEvalPlan":
+        if self._plan is None:
+            self._plan = ops.LogitsEvalPlan(self.index)
+        return self._plan
+
+    def _add_logits(self, logits: torch.Tensor, scorer, want_outputs: bool):
+        score, _, view = scorer
+        self._join_tail()
+        lv, p1, pred = ops.eval_rows(logits, self.index, max(TOPK))
+        score(lv, p1, pred)
+        return (pred, view(lv)) if want_outputs else None
+
+    def _add_images(self, imgs: torch.Tensor, scorer, want_outputs: bool):
+        score, reads, view = scorer
+        plan = self._fused_plan()
+        if not plan.supported:                        # a hierarchy beyond hgr_logits_eval's capacity: logits + hgr_eval_rows
+            return self._add_logits(self.model(imgs), scorer, want_outputs)
+        if not want_outputs and hasattr(self.model, "forward_eval_overlapped"):
+            # the loop's own route: the step as a two-stage pipeline (the class-token tail of this batch beside the next batch's tower);
+            # score runs on the tail's stream, so what it reads must outlive this call there; counters() / summary() join that stream
+            side = self.model._pipe_state(imgs.device).side
+            for t in reads:
+                t.record_stream(side)
+            if self.model.forward_eval_overlapped(imgs, plan, max(TOPK), score):
+                return None
+        self._join_tail()
+        lv, p1, pred = self.model.forward_eval(imgs, plan, max(TOPK))
+        score(lv, p1, pred)
+        return (pred, view(lv)) if want_outputs else None
+
     @torch.no_grad()
     def add_batch(self, logits: torch.Tensor, target: int, targets: Optional[torch.Tensor] = None, want_outputs: bool = True):
         """One iteration of main.py:131-191 on device.  ``target`` = the batch's single class
@@ -83,35 +153,7 @@ class Evaluator:
         top-1 over the train columns :157, arg-max per depth level :162-176) and hgr_eval_counters (hits, hit / path /
         point ratios :139-148,157-160,177-191).  Returns (pred_top20, dict_path) int32 tensors unless ``want_outputs``
         is False (the evaluation loop itself does not need them)."""
-        if hasattr(self.model, "join_tail"):
-            self.model.join_tail()
-        lv, p1, pred = ops.eval_rows(logits, self.index, max(TOPK))
-        parents, levels64, levels32, L = self._parents(target)
-        tg = None
-        if targets is not None:
-            tg = targets if targets.dtype == torch.int64 else targets.to(torch.int64)
-            tg = tg.contiguous()
-        ops.eval_counters(pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)
-        if self.report is not None:
-            self._report(pred, self._class_targets(tg, target, pred), p1, lv)
-        if not want_outputs:
-            return None
-        return pred, lv[:, levels64]                                                 # dict_path [B, L]
-
-    @staticmethod
-    def _row_targets(targets: torch.Tensor) -> torch.Tensor:
-        return (targets if targets.dtype == torch.int64 else targets.to(torch.int64)).contiguous().view(-1)
-
-    @staticmethod
-    def _class_targets(tg: Optional[torch.Tensor], target: int, like: torch.Tensor) -> torch.Tensor:
-        """The row targets of a single-class batch for the report: the ones given, else ``target`` for every row of ``like``."""
-        if tg is not None:
-            return tg.view(-1)
-        return torch.full((like.shape[0],), int(target), dtype=torch.int64, device=like.device)
-
-    def _report(self, pred, tg, p1, lv) -> None:
-        """One hgr_eval_report_rows launch on the current stream, on the outputs the counters were just advanced with."""
-        ops.eval_report_rows(pred, tg, p1.view(-1), lv, *self._ancestor_csr(), self.report)
+        return self._add_logits(logits, self._class_scorer(target, targets, logits), want_outputs)
 
     @torch.no_grad()
     def add_batch_rows(self, logits: torch.Tensor, targets: torch.Tensor, want_outputs: bool = False):
@@ -119,97 +161,32 @@ class Evaluator:
         own class, and hgr_eval_counters_rows scores each row against that class's path (the reference's counters are row-additive,
         main.py:139-191).  Rows with a target outside [0, n_nodes) are padding and count nothing.  Returns (pred_top20, level
         arg-max [B, n_levels]) with ``want_outputs``; the paths differ per row, so there is no dict_path view."""
-        if hasattr(self.model, "join_tail"):
-            self.model.join_tail()
-        lv, p1, pred = ops.eval_rows(logits, self.index, max(TOPK))
-        tg = self._row_targets(targets)
-        ops.eval_counters_rows(pred, tg, p1.view(-1), lv, *self._ancestor_csr(), self.acc)
-        if self.report is not None:
-            self._report(pred, tg, p1, lv)
-        return (pred, lv) if want_outputs else None
+        return self._add_logits(logits, self._rows_scorer(targets), want_outputs)
 
     def fused_ok(self) -> bool:
         """hgr_logits_eval needs an embedding width that is a multiple of 128 (<= 1024) and <= 32 levels."""
         d = self.model._zsl16.shape[1] if self.model._zsl16 is not None else 0
         if not (d % 128 == 0 and 128 <= d <= 1024 and self.n_levels <= 32 and self.index.n_test >= max(TOPK)):
             return False
-        if self._plan is None:
-            self._plan = ops.LogitsEvalPlan(self.index)
-        return self._plan.supported                  # <= 32 768 level-padded columns
+        return self._fused_plan().supported          # <= 32 768 level-padded columns
 
     @torch.no_grad()
     def add_images(self, imgs: torch.Tensor, target: int, targets: Optional[torch.Tensor] = None, want_outputs: bool = False):
         """One iteration of main.py:131-191 WITHOUT materialising the logits: image tower -> L2 norm -> hgr_logits_eval (the
         class-logits GEMM with top-20 / top-1 / per-level arg-max in its epilogue) -> hgr_eval_counters.  Same counters, bit for
         bit, as add_batch(model(imgs), ...); use add_batch when the caller needs the logits themselves."""
-        if self._plan is None:
-            self._plan = ops.LogitsEvalPlan(self.index)
-        if not self._plan.supported:                  # a hierarchy beyond hgr_logits_eval's capacity: logits + hgr_eval_rows
-            return self.add_batch(self.model(imgs), target, targets, want_outputs)
-        parents, levels64, levels32, L = self._parents(target)
-        tg = None
-        if targets is not None:
-            tg = (targets if targets.dtype == torch.int64 else targets.to(torch.int64)).contiguous()
-        if not want_outputs and hasattr(self.model, "forward_eval_overlapped"):
-            # the loop's own route: the step as a two-stage pipeline (the class-token tail of this batch beside the next batch's tower);
-            # the counters are advanced on the tail's stream, counters() / summary() join it
-            side = self.model._pipe_state(imgs.device)["side"]
-            if tg is not None:
-                tg.record_stream(side)
-            rt = None
-            if self.report is not None:
-                rt = self._class_targets(tg, target, imgs)   # made on this stream, ahead of the head: ordered before the tail reads it
-                rt.record_stream(side)
-                self._ancestor_csr()                          # uploaded (first use) on this stream, not on the tail's
-
-            def consume(lv, p1, pred):                        # on the tail's stream: the report directly behind the counters
-                ops.eval_counters(pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)
-                if rt is not None:
-                    self._report(pred, rt, p1, lv)
-            if self.model.forward_eval_overlapped(imgs, self._plan, max(TOPK), consume):
-                return None
-        if hasattr(self.model, "join_tail"):
-            self.model.join_tail()                      # the counters may still be in flight on the tail stream of earlier batches
-        lv, p1, pred = self.model.forward_eval(imgs, self._plan, max(TOPK))
-        ops.eval_counters(pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)
-        if self.report is not None:
-            self._report(pred, self._class_targets(tg, target, pred), p1, lv)
-        if not want_outputs:
-            return None
-        return pred, lv[:, levels64]
+        return self._add_images(imgs, self._class_scorer(target, targets, imgs), want_outputs)
 
     @torch.no_grad()
     def add_images_rows(self, imgs: torch.Tensor, targets: torch.Tensor, want_outputs: bool = False):
         """add_images for a batch packed from SEVERAL classes: the same three routes (two-graph pipeline, single graph, logits +
         hgr_eval_rows for a hierarchy beyond hgr_logits_eval's capacity), with hgr_eval_counters_rows in the place of
         hgr_eval_counters.  Same counters as add_batch_rows(model(imgs), targets)."""
-        if self._plan is None:
-            self._plan = ops.LogitsEvalPlan(self.index)
-        if not self._plan.supported:
-            return self.add_batch_rows(self.model(imgs), targets, want_outputs)
-        tg = self._row_targets(targets)
-        anc_ptr, anc_nodes, anc_levels = self._ancestor_csr()
-        if not want_outputs and hasattr(self.model, "forward_eval_overlapped"):
-            tg.record_stream(self.model._pipe_state(imgs.device)["side"])       # read by the counters on the tail's stream
-
-            def consume(lv, p1, pred):                        # on the tail's stream: the report directly behind the counters
-                ops.eval_counters_rows(pred, tg, p1.view(-1), lv, anc_ptr, anc_nodes, anc_levels, self.acc)
-                if self.report is not None:
-                    self._report(pred, tg, p1, lv)
-            if self.model.forward_eval_overlapped(imgs, self._plan, max(TOPK), consume):
-                return None
-        if hasattr(self.model, "join_tail"):
-            self.model.join_tail()
-        lv, p1, pred = self.model.forward_eval(imgs, self._plan, max(TOPK))
-        ops.eval_counters_rows(pred, tg, p1.view(-1), lv, anc_ptr, anc_nodes, anc_levels, self.acc)
-        if self.report is not None:
-            self._report(pred, tg, p1, lv)
-        return (pred, lv) if want_outputs else None
+        return self._add_images(imgs, self._rows_scorer(targets), want_outputs)
 
     def counters(self, group=None) -> Dict[str, float]:
         """Read the counters (one D2H copy); with a process group, all-reduce(sum) them first."""
-        if hasattr(self.model, "join_tail"):
-            self.model.join_tail()                      # pipelined steps advance the counters on the tail stream
+        self._join_tail()                               # pipelined steps advance the counters on the tail stream
         acc = self.acc
         if group is not None:
             import torch.distributed as dist
@@ -241,8 +218,7 @@ class Evaluator:
         """The hierarchy report's table as a CPU int64 tensor [ops.REPORT_LEN] (one D2H copy); with a process group the tables of
         all ranks are summed first - an int64 all-reduce, exact, on the device (nccl) as on CPU tensors (gloo)."""
         assert self.report is not None, "Evaluator(model, report=True) keeps the hierarchy report"
-        if hasattr(self.model, "join_tail"):
-            self.model.join_tail()                      # pipelined steps advance the table on the tail stream
+        self._join_tail()                               # pipelined steps advance the table on the tail stream
         table = self.report
         if group is not None:
             import torch.distributed as dist

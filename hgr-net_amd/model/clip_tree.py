@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import clip, ops
+from ..graphs import GraphCache
 from ..hierarchy import build_hierarchy
 from .._lib import HgrError
 
@@ -47,7 +48,46 @@ class _StopHead(Exception):
     """Raised by the split hook while the HEAD graph of a pipelined step is captured: the rest of the step belongs to the tail graph."""
 
 
+def _classifier_part(slot: str):
+    """``zsl_weights`` / ``_zsl16`` as properties: every assignment, by update_classifier() or from outside, moves the classifier
+    token that the split operand, the plans bound to it and both graph generations are keyed on.  (nn.Module.__setattr__ hands a
+    plain tensor on to object.__setattr__, which honours properties.)"""
+    def fget(self):
+        return self.__dict__.get(slot)
+
+    def fset(self, value):
+        self.__dict__[slot] = value
+        self.__dict__["_cls_token"] = self.__dict__.get("_cls_token", 0) + 1
+    return property(fget, fset)
+
+
+class _Pipe:
+    """State of the two-stage evaluation pipeline (forward_eval_overlapped): the side stream of the tails, the graphs of both step
+    parities and the events that order a head behind the tail that last read its workspace set."""
+
+    def __init__(self, dev):
+        # the tail's launches are a few dozen workgroups each: a high-priority stream lets them take the first slots that free up
+        self.side = torch.cuda.Stream(device=dev, priority=int(os.environ.get("HGR_TAIL_PRIO", "-1")))
+        # 8 entries over two parities, all dropped when full: their graphs may be in flight on either stream
+        self.cache = GraphCache(8, "all", pre_drop=self.drain)
+        self.ok = None            # whether the step has a split point (learnt per generation from the head phase)
+        self.step = 0
+        self.head_done = [torch.cuda.Event(), torch.cuda.Event()]
+        self.tail_done = [torch.cuda.Event(), torch.cuda.Event()]
+        for e in self.tail_done:
+            e.record()
+
+    def drain(self) -> None:
+        """The current stream behind the side stream, and idle: nothing captured so far is in flight afterwards."""
+        main = torch.cuda.current_stream()
+        main.wait_stream(self.side)
+        main.synchronize()
+
+
 class tree_model(nn.Module):
+    zsl_weights = _classifier_part("_cls_zsl32")
+    _zsl16 = _classifier_part("_cls_zsl16")
+
     def __init__(self, opts, candidates_train: Sequence[str], candidates_test: Sequence[str],
                  node_tokens: Optional[torch.Tensor] = None, clip_model: Optional[nn.Module] = None):
         super().__init__()
@@ -118,8 +158,8 @@ class tree_model(nn.Module):
         self.zsl_weights = None
         self._zsl16 = None
         self.use_graph = os.environ.get("HGR_GRAPH", "1") != "0"     # replay forward() as a HIP graph (HGR_GRAPH=0: eager launches)
-        self._graphs, self._graph_gen, self._graph_misses, self._graph_static = {}, None, 0, None
-        self._pipe = None            # state of the two-stage evaluation pipeline (forward_eval_overlapped)
+        self._graph_cache = GraphCache(4, "oldest")      # forward() / forward_eval(): one graph per input buffer, the oldest goes first
+        self._pipe = None            # _Pipe of the two-stage evaluation pipeline (forward_eval_overlapped), made on first use
 
     @staticmethod
     def _wordnet_name(wnid: str) -> str:
@@ -139,7 +179,11 @@ class tree_model(nn.Module):
     def update_classifier(self, group=None):
         """Text-encode every node prompt, L2-normalise rows -> ``zsl_weights`` [N, D] fp32
         (clip_tree.py:318-325).  With a process ``group`` each rank encodes N/world rows and the rows
-        are all-gathered over RCCL (hgr_net_amd.parallel)."""
+        are all-gathered over RCCL (hgr_net_amd.parallel).
+
+        A classifier is always REPLACED: assigning ``zsl_weights`` / ``_zsl16`` (here or from outside) moves the classifier token
+        every dependent cache and graph generation is keyed on.  Rewriting the installed tensors in place through a raw pointer is
+        not supported - nothing would notice (parameters have ops.WEIGHTS_GEN for that)."""
         n = len(self.nodes)
         if group is not None:
             from ..parallel import sharded_text_features
@@ -177,46 +221,31 @@ class tree_model(nn.Module):
             return self._forward_graphed(inputs, True, ("eval", plan, k))
         return self._forward_eager(inputs, ("eval", plan, k))
 
+    def _generation(self, inputs, mode):
+        """What the graphs of both routes are bound to: input shape and dtype, the classifier (token), the workspace buffers (epoch),
+        the prepared weights, the tower variant and the evaluation mode with its plan (held, so compared by identity and kept alive).
+        Taken AFTER the eager warm-up of a new generation: the warm-up builds the prepared weights and may (re)allocate workspace
+        buffers, both of which move the key."""
+        cm = self.clip_model
+        return (tuple(inputs.shape), inputs.dtype, self._cls_token, cm._ws.epoch, cm._fingerprint(), tuple(sorted(cm._ln_off)), mode)
+
     def _forward_graphed(self, inputs, static_output: bool = False, mode=None):
         """The ~100 launches of one forward replayed as a HIP graph: no host launch cost and no inter-kernel gaps
-        (+6 % on the ViT-B/32 step).  Same kernels, same bits.  A graph is bound to the buffers it was captured on, so
-        graphs live for one generation = (input shape, dtype, classifier, prepared weights): anything else clears them
-        (the warm-up run may also have re-allocated workspace buffers older graphs point into).  Inside a generation up
-        to 4 graphs are keyed by the input buffer's address - loaders recycle a few buffers; after 8 misses in a row the
-        input is copied into one static buffer instead.  The logits are returned as a fresh tensor unless the caller passes
-        ``static_output=True`` (it consumes them before the next forward: the evaluation loop does)."""
-        def generation():
-            return (tuple(inputs.shape), inputs.dtype, self._zsl16.data_ptr(), self.clip_model._ws.epoch, self.clip_model._fingerprint(),
-                    tuple(sorted(self.clip_model._ln_off)), None if mode is None else (mode[0], id(mode[1]), mode[1].zsl.data_ptr(), mode[2]))
-
+        (+6 % on the ViT-B/32 step).  Same kernels, same bits.  Which graph replays is graphs.GraphCache's policy: one generation
+        (_generation) at a time, inside it up to 4 graphs keyed by the input buffer's address, a static input buffer once addresses
+        never repeat.  The logits are returned as a fresh tensor unless the caller passes ``static_output=True`` (it consumes them
+        before the next forward: the evaluation loop does)."""
         self.clip_model.poll_ln_guard()          # every 64th call: a tripped range guard switches the tower (and moves the generation below)
-
-        if generation() != self._graph_gen:
-            # warm-up BEFORE the key is fixed: it builds the prepared weights and may (re)allocate workspace buffers, both of
-            # which move the key; graphs captured afterwards then see a stable generation.  A direct encode_image call with
-            # a larger batch between two forwards re-allocates the workspace -> epoch moves -> stale graphs are dropped here.
-            self._graphs.clear()
+        cache = self._graph_cache
+        if cache.renew(self._generation(inputs, mode)):
+            # e.g. a direct encode_image call with a larger batch between two forwards re-allocated the workspace -> epoch moved ->
+            # the stale graphs are gone.  Warm-up BEFORE the key is fixed (see _generation); graphs captured afterwards see a
+            # stable generation.
             self._forward_eager(inputs, mode)
-            self._graph_gen, self._graph_misses, self._graph_static = generation(), 0, None
-        ent = self._graphs.get(inputs.data_ptr())
-        if ent is None:
-            self._graph_misses += 1
-            if self._graph_misses > 8:                          # addresses never repeat: one static input buffer
-                if self._graph_static is None:
-                    buf = torch.empty_like(inputs)
-                    buf.copy_(inputs)
-                    self._graph_static = (buf,) + self._capture(buf, mode)
-                buf, g, out = self._graph_static
-                buf.copy_(inputs)
-                g.replay()
-                return out if (static_output or mode is not None) else out.clone()
-            if len(self._graphs) >= 4:
-                self._graphs.pop(next(iter(self._graphs)))
-            ent = self._graphs[inputs.data_ptr()] = self._capture(inputs, mode)
-        else:
-            self._graph_misses = 0
-        ent[0].replay()
-        return ent[1] if (static_output or mode is not None) else ent[1].clone()
+            cache.gen = self._generation(inputs, mode)
+        g, out = cache.lookup(inputs, 0, lambda buf, slot: self._capture(buf, mode))
+        g.replay()
+        return out if (static_output or mode is not None) else out.clone()
 
     # ---------------------------------------------------------------------------------------------
     # evaluation steps as a two-stage pipeline
@@ -249,20 +278,15 @@ class tree_model(nn.Module):
             ops.SPLIT_HOOK, self.clip_model._img_tag = prev_hook, prev_tag
         return out, bool(seen)
 
-    def _pipe_state(self, dev):
+    def _pipe_state(self, dev) -> _Pipe:
         if self._pipe is None:
-            # the tail's launches are a few dozen workgroups each: a high-priority stream lets them take the first slots that free up
-            side = torch.cuda.Stream(device=dev, priority=int(os.environ.get("HGR_TAIL_PRIO", "-1")))
-            self._pipe = {"side": side, "graphs": {}, "gen": None, "ok": None, "step": 0, "misses": 0, "static": {},
-                          "head_done": [torch.cuda.Event(), torch.cuda.Event()], "tail_done": [torch.cuda.Event(), torch.cuda.Event()]}
-            for e in self._pipe["tail_done"]:
-                e.record()
+            self._pipe = _Pipe(dev)
         return self._pipe
 
     def join_tail(self) -> None:
         """Order the current stream behind every tail launched so far (readers of the evaluation counters call this)."""
         if self._pipe is not None:
-            torch.cuda.current_stream().wait_stream(self._pipe["side"])
+            torch.cuda.current_stream().wait_stream(self._pipe.side)
 
     @torch.no_grad()
     def forward_eval_overlapped(self, inputs, plan, k: int, consume) -> bool:
@@ -289,66 +313,45 @@ class tree_model(nn.Module):
         mode = ("eval", plan, k)
         st = self._pipe_state(inputs.device)
         self.clip_model.poll_ln_guard()
-        gen = (tuple(inputs.shape), inputs.dtype, self._zsl16.data_ptr(), self.clip_model._fingerprint(), tuple(sorted(self.clip_model._ln_off)),
-               id(plan), plan.zsl.data_ptr(), k)
         main = torch.cuda.current_stream()
-        if gen != st["gen"]:
-            # new generation (shape, classifier, weights): both workspace sets exist after one eager step each; whether the step has
-            # a split point is learnt from the head phase
-            main.wait_stream(st["side"])
-            st["graphs"].clear()
-            st["static"].clear()
-            st["misses"] = 0
+        if self._generation(inputs, mode) != st.cache.gen:
+            # new generation (shape, classifier, weights, workspace): both workspace sets exist after one eager step each; whether the
+            # step has a split point is learnt from the head phase
+            main.wait_stream(st.side)
             ok = True
             for tag in ("v", "v@1"):
                 ok &= self._eager_phase(inputs, mode, "head", tag)[1]
                 if ok:
                     self._eager_phase(inputs, mode, "tail", tag)
-            main.synchronize()
-            st["gen"], st["ok"] = gen, ok
-        if not st["ok"]:
+            main.synchronize()                                  # behind the side stream and idle: the old generation's graphs can go
+            st.cache.renew(self._generation(inputs, mode))
+            st.ok = ok
+        if not st.ok:
             return False
-        par = st["step"] & 1
-        st["step"] += 1
-        tag = "v@1" if par else "v"
-        key = (inputs.data_ptr(), par, self.clip_model._ws.epoch)
-        ent = st["graphs"].get(key)
-        if ent is None:
-            st["misses"] += 1
-            if st["misses"] > 8:                              # input addresses never repeat: one static input buffer per parity
-                buf = st["static"].get(par)
-                if buf is None:
-                    buf = st["static"][par] = torch.empty_like(inputs)
-                buf.copy_(inputs)                             # on the caller's stream, behind the head that last read it
-                inputs = buf
-                key = (buf.data_ptr(), par, self.clip_model._ws.epoch)
-                ent = st["graphs"].get(key)
-        else:
-            st["misses"] = 0
-        if ent is None:
-            if len(st["graphs"]) >= 8:
-                main.wait_stream(st["side"])
-                st["graphs"].clear()
-            main.wait_stream(st["side"])
-            main.synchronize()
+        par = st.step & 1
+        st.step += 1
+
+        def capture(buf, par):
+            tag = "v@1" if par else "v"
+            epoch = self.clip_model._ws.epoch
+            st.drain()
             gh, gt = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(gh):
-                self._eager_phase(inputs, mode, "head", tag)
+                self._eager_phase(buf, mode, "head", tag)
             with torch.cuda.graph(gt):
-                outs, _ = self._eager_phase(inputs, mode, "tail", tag)
-            if key[2] != self.clip_model._ws.epoch:          # a capture re-allocated a workspace buffer: the warm-up above should have made that impossible
+                outs, _ = self._eager_phase(buf, mode, "tail", tag)
+            if epoch != self.clip_model._ws.epoch:          # a capture re-allocated a workspace buffer: the warm-up above should have made that impossible
                 raise HgrError("workspace buffers moved during the capture of a pipelined evaluation step")
-            ent = st["graphs"][key] = (gh, gt, outs)
-        gh, gt, outs = ent
-        main.wait_event(st["tail_done"][par])               # the tail that last read this workspace set (step i - 2)
+            return gh, gt, outs
+        gh, gt, outs = st.cache.lookup(inputs, par, capture)
+        main.wait_event(st.tail_done[par])                  # the tail that last read this workspace set (step i - 2)
         gh.replay()
-        st["head_done"][par].record(main)
-        side = st["side"]
-        with torch.cuda.stream(side):
-            side.wait_event(st["head_done"][par])
+        st.head_done[par].record(main)
+        with torch.cuda.stream(st.side):
+            st.side.wait_event(st.head_done[par])
             gt.replay()
             consume(*outs)
-            st["tail_done"][par].record(side)
+            st.tail_done[par].record(st.side)
         return True
 
     def _capture(self, inputs, mode=None):
@@ -360,11 +363,12 @@ class tree_model(nn.Module):
         return g, out
 
     def _eval_class_operand(self):
-        """The 16-bit class matrix hgr_logits_eval multiplies with: `_zsl16`, or with HGR_LOGITS_SPLIT its K-concatenated form."""
+        """The 16-bit class matrix hgr_logits_eval multiplies with: `_zsl16`, or with HGR_LOGITS_SPLIT its K-concatenated form (made
+        once per classifier token; a new classifier gets a new tensor object, which is what LogitsEvalPlan.bind looks at)."""
         split = LOGITS_SPLIT if (LOGITS_SPLIT in ("class", "feat") and 2 * self._zsl16.shape[1] <= 1024) else ""
         if not split:
             return self._zsl16
-        key = (split, self._zsl16.data_ptr(), self._zsl16._version, self.zsl_weights.data_ptr(), self.zsl_weights._version)
+        key = (split, self._cls_token)
         if getattr(self, "_zsl_split_key", None) != key:
             z16 = self._zsl16
             second = (self.zsl_weights.float() - z16.float()).to(z16.dtype) if split == "class" else z16

@@ -456,7 +456,7 @@ class LogitsEvalPlan:
     """Level-sorted view of the class matrix for hgr_logits_eval (include/hgr.h): the column permutation (levels contiguous, each
     padded to a multiple of 32 columns, total to a multiple of 96 = one CU's slab), the per-column train / test positions in permuted
     order and the first 32-column slice of every level.  Built once per model from an EvalIndex; `bind(zsl16)` gathers the permuted
-    16-bit class matrix (once per update_classifier)."""
+    16-bit class matrix (once per tensor object handed in, i.e. once per update_classifier)."""
     SLICE, SLAB = 32, 96
 
     def __init__(self, index: EvalIndex):
@@ -501,11 +501,10 @@ class LogitsEvalPlan:
         """``algo_d``: the embedding width the product stands for when zsl16 is a K-concatenated operand (clip_tree.LOGITS_SPLIT) -
         profiling reports the ALGORITHMIC flops 2 B N D, not the doubled K."""
         self.algo_d = int(algo_d or zsl16.shape[1])
-        key = (zsl16.data_ptr(), zsl16._version, tuple(zsl16.shape))
-        if self._src != key:
+        if self._src is not zsl16:                   # the tensor OBJECT it was given (held): a new classifier is a new tensor
             z = zsl16[self.perm]
             z[~self.valid] = 0
-            self.zsl, self._src = z.contiguous(), key
+            self.zsl, self._src = z.contiguous(), zsl16
         return self
 
     def workspace(self, rows: int, dev) -> torch.Tensor:

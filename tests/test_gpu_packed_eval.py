@@ -200,7 +200,7 @@ class _Recorder(evaluate.Evaluator):
     def _note(self, imgs):
         m = self.model
         self.shapes.append(tuple(imgs.shape))
-        self.gens.append(((m._pipe or {}).get("gen"), m._graph_gen))
+        self.gens.append((m._pipe.cache.gen if m._pipe is not None else None, m._graph_cache.gen))
 
     def add_images_rows(self, imgs, targets, want_outputs=False):
         out = super().add_images_rows(imgs, targets, want_outputs)
