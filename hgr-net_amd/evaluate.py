@@ -21,11 +21,45 @@ from .utils import count_acc
 
 TOPK = (1, 2, 5, 10, 20)
 COUNTERS = ["hits@1", "hits@2", "hits@5", "hits@10", "hits@20", "hits_all", "path_all", "point_all", "num_sample"]
+DECODES = ("flat", "path")
+# the weights of path decoding: tree_model.get_weights' methods, and "self" (all weight on the node itself: path scores = logits)
+DECODE_WEIGHTS = ("equal", "increasing", "decreasing", "nl_increasing", "nl_decreasing", "adaptive", "self")
+
+
+@torch.no_grad()
+def path_weight_table(model, method: str) -> torch.Tensor:
+    """The weight table of hgr_path_scores, fp32 [ops.PATH_MAXL + 1, ops.PATH_MAXL] on the model's device: row L, for every path
+    length L = 1 .. max_depth + 1 of the model's hierarchy, is ``model.get_weights(method, L)`` bit for bit (column 0 = the top-most
+    ancestor, column L - 1 = the node itself); every other entry is 0.  ``"self"`` - one-hot at column L - 1 - exists here only: it
+    is no training weighting.  ``"adaptive"`` is made from ``model.layer_weight`` by tensor operations, without a host read."""
+    if method not in DECODE_WEIGHTS:
+        raise ValueError(f"decode_weights {method!r}: one of {DECODE_WEIGHTS}")
+    if method == "adaptive" and not hasattr(model, "layer_weight"):
+        raise ValueError("decode_weights 'adaptive' needs a model built with opts.weights == 'adaptive' (model.layer_weight)")
+    dev = model.train_index.device
+    n_rows = model.max_depth + 1
+    assert n_rows <= ops.PATH_MAXL, "a path holds at most 32 nodes"
+    tab = torch.zeros((ops.PATH_MAXL + 1, ops.PATH_MAXL), dtype=torch.float32, device=dev)
+    for L in range(1, n_rows + 1):
+        if method == "self":
+            tab[L, L - 1] = 1.0
+        else:
+            tab[L, :L] = model.get_weights(method, L).detach().to(device=dev, dtype=torch.float32)
+    return tab
 
 
 class Evaluator:
-    def __init__(self, model, report: bool = False):
+    def __init__(self, model, report: bool = False, decode: str = "flat", decode_weights: str = "increasing"):
+        """``decode``: what the predictions are taken from - "flat": the logits (the reference); "path": the path scores of
+        hgr_path_scores, every node scored by the ``decode_weights``-weighted logits along its root-to-node path.  Everything behind
+        hgr_eval_rows (counters, report, packed batches, all-reduces) is the same for both."""
+        if decode not in DECODES:
+            raise ValueError(f"decode {decode!r}: one of {DECODES}")
         self.model = model
+        self.decode = decode
+        # path decoding: the weight table, made once, and one scores buffer, grown to the largest batch seen; flat: nothing extra
+        self._wtab = path_weight_table(model, decode_weights) if decode == "path" else None
+        self._scores = None
         dev = model.train_index.device
         self.acc = torch.zeros(len(COUNTERS), dtype=torch.float64, device=dev)
         # the hierarchy report (hgr_eval_report_rows): an int64 table advanced beside the counters, or None = nothing extra is launched
@@ -121,15 +155,29 @@ class Evaluator:
             self._plan = ops.LogitsEvalPlan(self.index)
         return self._plan
 
+    def path_scores(self, logits: torch.Tensor) -> torch.Tensor:
+        """hgr_path_scores of ``logits`` [B, >= N] with this Evaluator's weight table, into its scores buffer: valid until the next
+        batch.  One launch; the ancestor CSR is the report's."""
+        assert self._wtab is not None, "Evaluator(model, decode='path') keeps the weight table"
+        rows, n = logits.shape[0], self.index.n_nodes
+        if self._scores is None or self._scores.numel() < rows * n or self._scores.device != logits.device:
+            self._scores = torch.empty(rows * n, dtype=torch.float32, device=logits.device)
+        ptr, nodes, _ = self._ancestor_csr()
+        return ops.path_scores(logits, ptr, nodes, self._wtab, out=self._scores[:rows * n].view(rows, n))
+
     def _add_logits(self, logits: torch.Tensor, scorer, want_outputs: bool):
         score, _, view = scorer
         self._join_tail()
+        if self.decode == "path":                      # path decoding IS hgr_eval_rows on the path scores
+            logits = self.path_scores(logits)
         lv, p1, pred = ops.eval_rows(logits, self.index, max(TOPK))
         score(lv, p1, pred)
         return (pred, view(lv)) if want_outputs else None
 
     def _add_images(self, imgs: torch.Tensor, scorer, want_outputs: bool):
         score, reads, view = scorer
+        if self.decode == "path":                     # the fused kernel never has the whole row: logits -> path scores -> hgr_eval_rows
+            return self._add_logits(self.model(imgs, None, static_output=True), scorer, want_outputs)
         plan = self._fused_plan()
         if not plan.supported:                        # a hierarchy beyond hgr_logits_eval's capacity: logits + hgr_eval_rows
             return self._add_logits(self.model(imgs), scorer, want_outputs)
@@ -164,7 +212,10 @@ class Evaluator:
         return self._add_logits(logits, self._rows_scorer(targets), want_outputs)
 
     def fused_ok(self) -> bool:
-        """hgr_logits_eval needs an embedding width that is a multiple of 128 (<= 1024) and <= 32 levels."""
+        """hgr_logits_eval needs an embedding width that is a multiple of 128 (<= 1024) and <= 32 levels - and flat decoding: the path
+        scores of a column read other columns of its row, which the fused kernel never holds together."""
+        if self.decode == "path":
+            return False
         d = self.model._zsl16.shape[1] if self.model._zsl16 is not None else 0
         if not (d % 128 == 0 and 128 <= d <= 1024 and self.n_levels <= 32 and self.index.n_test >= max(TOPK)):
             return False
@@ -296,6 +347,26 @@ def format_report(rep: dict) -> str:
 
 
 @torch.no_grad()
+def predict(model, imgs: torch.Tensor, k: int = max(TOPK), decode: str = "flat", decode_weights: str = "increasing",
+            want_scores: bool = False, evaluator: Optional[Evaluator] = None) -> Dict[str, torch.Tensor]:
+    """Classify a batch of images (after ``model.update_classifier()``): {"topk": int32 [B, k] node ids among the test classes, best
+    first, "top1": int32 [B] the best train class, "levels": int32 [B, n_levels] the best train class of every depth level (the
+    reference's -1 filler competes, as in hgr_eval_rows)} - hgr_eval_rows on the logits (``decode="flat"``) or on their path scores (``"path"``, weights
+    ``decode_weights``).  ``want_scores`` adds "scores": fp32 [B, N], what the predictions were taken from.  ``evaluator``: an
+    Evaluator of this model to reuse (its index, weight table and scores buffer; its decode settings then hold) - without one, a
+    new one is built per call."""
+    ev = evaluator if evaluator is not None else Evaluator(model, decode=decode, decode_weights=decode_weights)
+    scores = model(imgs.to(model.train_index.device), None, static_output=True)
+    if ev.decode == "path":
+        scores = ev.path_scores(scores)
+    lv, p1, topk = ops.eval_rows(scores, ev.index, k)
+    out = {"topk": topk, "top1": p1.view(-1), "levels": lv}
+    if want_scores:
+        out["scores"] = scores[:, :ev.index.n_nodes].clone()          # the logits / the scores buffer are reused by the next batch
+    return out
+
+
+@torch.no_grad()
 def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, group=None, log: bool = True) -> str:
     """Drop-in for the reference's ``test(opts, model, device, splits)`` (main.py:104-222).
     ``loader`` yields the reference's batch dicts {'img': [1,B,3,R,R], 'label': [1,B]}.  With ``opts.pack_batches`` the batches are
@@ -320,7 +391,11 @@ def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, gr
         print("number of batches:{}".format(loader.batch_sampler.num_batch))
     print("Running.", flush=True)
     report_path = getattr(opts, "hier_report", None)
-    ev = Evaluator(model, report=True) if report_path else Evaluator(model)
+    decode, decode_weights = getattr(opts, "decode", "flat"), getattr(opts, "decode_weights", "increasing")
+    kw = {"report": True} if report_path else {}
+    if decode != "flat":
+        kw.update(decode=decode, decode_weights=decode_weights)
+    ev = Evaluator(model, **kw)
     fused = ev.fused_ok() and os.environ.get("HGR_EVAL_FUSED", "1") != "0"
     packed = bool(getattr(opts, "pack_batches", False))
     if packed:
@@ -345,6 +420,8 @@ def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, gr
         ev.add_batch(logits, target, targets, want_outputs=False)
     print("End of testing.")
     out = ev.summary(group)
+    if decode != "flat":
+        print("decode: {} ({})".format(decode, decode_weights))
     print(out, flush=True)
     if report_path:                                      # every rank joins the all-reduce, rank 0 writes
         rep = ev.report_dict(group)

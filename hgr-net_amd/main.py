@@ -17,7 +17,7 @@ import os
 import torch
 
 from . import synth
-from .evaluate import test
+from .evaluate import DECODE_WEIGHTS, DECODES, test
 from .model import tree_model
 from .training import FusedAdamW
 from .utils import cosine_lr
@@ -80,6 +80,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--hier_report", default=None, type=str, metavar="PATH",
                    help="evaluation: also count per depth, per path level and by tree distance of the mistakes (hgr_eval_report_rows) and "
                         "write the report as JSON to PATH")
+    p.add_argument("--decode", default="flat", type=str, choices=list(DECODES),
+                   help="evaluation: predict from the logits (flat, the reference) or from the path scores (path, hgr_path_scores: every "
+                        "node scored by the weighted logits along its root-to-node path)")
+    p.add_argument("--decode_weights", default="increasing", type=str, choices=list(DECODE_WEIGHTS),
+                   help="--decode path: the weights along a path, top-most ancestor first (get_weights' methods; self = the node alone)")
     p.add_argument("--ref_quirks", default=False, action="store_true",
                    help="reproduce the reference's missing zero_grad() (gradients accumulate across steps, SURVEY F11-i)")
     return p

@@ -590,6 +590,29 @@ def eval_report_rows(pred: torch.Tensor, targets: torch.Tensor, top1: torch.Tens
               _dev(anc_nodes), _dev(anc_levels), anc_ptr.numel() - 1, _dev(table), pred.shape[0], _stream())
 
 
+PATH_MAXL = 32                      # HGR_PATH_MAXL of include/hgr.h (= REPORT_MAXL): the longest path a weight table has a row for
+
+
+def path_scores(logits: torch.Tensor, anc_ptr: torch.Tensor, anc_nodes: torch.Tensor, wtab: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Path scores [rows, n_nodes] fp32 (hgr_path_scores, definition in include/hgr.h): every node scored by the weighted logits along
+    its root-to-node path, P(n) = anc_nodes[anc_ptr[n]:anc_ptr[n + 1]], with row L of ``wtab`` [33, 32] as the weights of a path of L
+    nodes; a node without a path of 1..32 nodes keeps its logit.  ``logits`` and ``out`` may be views of wider buffers (unit column
+    stride, at least n_nodes columns; further columns of ``out`` are left alone) and must not overlap.  Returns out[:, :n_nodes]."""
+    n_nodes = anc_ptr.numel() - 1
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[1] >= n_nodes >= 1
+    assert anc_ptr.dtype == anc_nodes.dtype == torch.int32 and anc_ptr.is_contiguous() and anc_nodes.is_contiguous()
+    assert wtab.dtype == torch.float32 and wtab.shape == (PATH_MAXL + 1, PATH_MAXL) and wtab.is_contiguous()
+    rows = logits.shape[0]
+    if out is None:
+        out = torch.empty((rows, n_nodes), dtype=torch.float32, device=logits.device)
+    assert out.dim() == 2 and out.dtype == torch.float32 and out.stride(1) == 1 and out.shape[0] == rows and out.shape[1] >= n_nodes
+    # the strides go to the library as they are: it rejects rows = 0, a leading dimension below n_nodes and overlapping operands
+    _lib.call("hgr_path_scores", _dev(logits), logits.stride(0), _dev(out), out.stride(0), n_nodes, _dev(anc_ptr), _dev(anc_nodes),
+              _dev(wtab), rows, _stream())
+    return out[:, :n_nodes]
+
+
 # ---- ModifiedResNet (RN) tower -------------------------------------------------------------------
 def conv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, b: int, h: int, wd: int, c: int,
                  stride: int = 1) -> torch.Tensor:

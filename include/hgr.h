@@ -310,6 +310,26 @@ int hgr_eval_report_rows(const int32_t *pred, int k, const int64_t *targets, con
                          const int32_t *anc_ptr, const int32_t *anc_nodes, const int32_t *anc_levels, int n_nodes, int64_t *table,
                          int rows, void *stream);
 
+/* Path scores: every node scored by the weighted evidence along its root-to-node path - the ancestor gather-reduce on [rows, N] that
+ * hierarchy-path decoding is hgr_eval_rows applied to.  logits fp32 [rows, ld], scores fp32 [rows, ld_out] (columns
+ * n_nodes .. ld_out - 1 are not written), anc_ptr int32 [n_nodes + 1] / anc_nodes int32: the CSR of hgr_eval_counters_rows,
+ * P(n) = anc_nodes[anc_ptr[n] : anc_ptr[n + 1]] (ancestors from the top down, then n), L its length; wtab fp32 [33][32]: row L holds
+ * the weights of a path of length L, column 0 the top-most ancestor, column L - 1 the node itself.  For row r, node n:
+ *   L < 1 or L > 32 : S[r, n] = x[r, n]                                  (pass-through, the sibling kernels' padding rule)
+ *   otherwise       : acc = 0.0f
+ *                     for j = 0 .. L - 1 in this order:
+ *                         a = P(n)[j]
+ *                         if (unsigned)a < n_nodes: acc = fmaf(wtab[L][j], x[r, a], acc)     (one rounding per term)
+ *                     S[r, n] = acc
+ * The order and the single rounding per term are part of the contract: S does not depend on how rows and columns fall onto lanes,
+ * workgroups and launches.  With convex weights (non-negative, sum 1) and cosine logits S stays in [-1, 1], so the -1 filler rule of
+ * hgr_eval_rows keeps its meaning.  Rejected before anything is launched: a null operand, rows < 1, n_nodes < 1, ld or ld_out <
+ * n_nodes, and scores overlapping logits (the byte ranges [logits, logits + rows * ld) and [scores, scores + rows * ld_out) must
+ * not intersect: the gathers read other columns of the row, so in place is wrong).  One node column per lane, 4 rows per group. */
+#define HGR_PATH_MAXL 32   /* = HGR_REPORT_MAXL */
+int hgr_path_scores(const float *logits, int64_t ld, float *scores, int64_t ld_out, int n_nodes, const int32_t *anc_ptr,
+                    const int32_t *anc_nodes, const float *wtab /* [33][32] */, int rows, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * ModifiedResNet (RN50) tower, clip/model.py:93-150.  Activations are NHWC 16-bit ([B, H, W, C] =
  * a row-major [B*H*W, C] matrix), so every 1x1 convolution IS hgr_gemm_nt; inference BatchNorm
