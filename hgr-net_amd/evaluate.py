@@ -49,12 +49,19 @@ def path_weight_table(model, method: str) -> torch.Tensor:
 
 
 class Evaluator:
-    def __init__(self, model, report: bool = False, decode: str = "flat", decode_weights: str = "increasing"):
+    def __init__(self, model, report: bool = False, decode: str = "flat", decode_weights: str = "increasing", hedge=None,
+                 hedge_temperature: Optional[float] = None):
         """``decode``: what the predictions are taken from - "flat": the logits (the reference); "path": the path scores of
         hgr_path_scores, every node scored by the ``decode_weights``-weighted logits along its root-to-node path.  Everything behind
-        hgr_eval_rows (counters, report, packed batches, all-reduces) is the same for both."""
+        hgr_eval_rows (counters, report, packed batches, all-reduces) is the same for both.
+        ``hedge``: 1..8 thresholds in (0, 1], strictly increasing - hedged predictions (hgr_subtree_hedge on what hgr_eval_rows gets,
+        candidates = the test classes; hgr_hedge_counters_rows behind the counters), read with hedge_table() / hedge_dict().
+        ``hedge_temperature``: the softmax's, default the model's ``logit_scale.exp()``, read once here."""
         if decode not in DECODES:
             raise ValueError(f"decode {decode!r}: one of {DECODES}")
+        thr = None if hedge is None else ops.hedge_thresholds(hedge)          # ValueError before anything is allocated
+        if hedge is not None and hedge_temperature is not None and not (0.0 < float(hedge_temperature) < float("inf")):
+            raise ValueError(f"hedge_temperature {hedge_temperature!r}: finite, > 0")
         self.model = model
         self.decode = decode
         # path decoding: the weight table, made once, and one scores buffer, grown to the largest batch seen; flat: nothing extra
@@ -64,6 +71,14 @@ class Evaluator:
         self.acc = torch.zeros(len(COUNTERS), dtype=torch.float64, device=dev)
         # the hierarchy report (hgr_eval_report_rows): an int64 table advanced beside the counters, or None = nothing extra is launched
         self.report = torch.zeros(ops.REPORT_LEN, dtype=torch.int64, device=dev) if report else None
+        # hedged predictions: thresholds (fixed point, on the device), temperature, the int64 outcome table [T, HEDGE_COLS] and the pick
+        # buffers of the current batch (grown to the largest batch seen) - or None = nothing is allocated, nothing extra is launched
+        self.hedge = None if hedge is None else tuple(float(t) for t in hedge)
+        self.hedge_temperature = self._hedge_thr = self.hedge_tab = self._hedge_pick = None
+        if thr is not None:
+            self.hedge_temperature = float(model.clip_model.logit_scale.detach().exp()) if hedge_temperature is None else float(hedge_temperature)
+            self._hedge_thr = torch.tensor(thr, dtype=torch.int32).to(dev)
+            self.hedge_tab = torch.zeros((len(thr), ops.HEDGE_COLS), dtype=torch.int64, device=dev)
         self.n_levels = model.max_depth + 1
         self.index = ops.EvalIndex(model.depth32, model.train_index32, model.test_index32, self.n_levels)   # dense per-column maps, built once
         self._anc = None         # ancestor paths of every node as a device CSR (see _ancestor_tables)
@@ -111,7 +126,7 @@ class Evaluator:
         return nodes[o:o + n], lv64[o:o + n], lv32[o:o + n], n
 
     # ---- scoring: two scorers x three routes -----------------------------------------------------------------------------------------
-    # A scorer is (score(lv, p1, pred), [tensors score reads that this batch made], view(lv)): score advances the counters and, directly
+    # A scorer is (score(lv, p1, pred, pick=None), [tensors score reads that this batch made], view(lv)): score advances the counters and, directly
     # behind them on the same stream, the report (if kept); view gives the level output the caller gets back.  Scorers are built on the
     # CALLER's stream before anything of the step is launched: whatever they make there (converted targets, the report's row targets,
     # the first upload of the ancestor CSR) is ordered ahead of the head, hence ahead of the tail that reads it.
@@ -124,14 +139,16 @@ class Evaluator:
         parents, levels64, levels32, _ = self._parents(target)
         tg = None if targets is None else self._row_targets(targets)
         rt = csr = None
-        if self.report is not None:                  # the report scores rows: without targets, ``target`` for every row
+        if self.report is not None or self.hedge is not None:    # both score rows: without targets, ``target`` for every row
             rt = tg if tg is not None else torch.full((like.shape[0],), int(target), dtype=torch.int64, device=like.device)
             csr = self._ancestor_csr()
 
-        def score(lv, p1, pred):
+        def score(lv, p1, pred, pick=None):
             ops.eval_counters(pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)
-            if rt is not None:
+            if self.report is not None:
                 ops.eval_report_rows(pred, rt, p1.view(-1), lv, *csr, self.report)
+            if pick is not None:
+                ops.hedge_counters_rows(pick, rt, csr[0], csr[1], self.hedge_tab)
         return score, [t for t in (tg, rt) if t is not None], lambda lv: lv[:, levels64]        # dict_path [B, L]
 
     def _rows_scorer(self, targets: torch.Tensor):
@@ -139,10 +156,12 @@ class Evaluator:
         tg = self._row_targets(targets)
         csr = self._ancestor_csr()
 
-        def score(lv, p1, pred):
+        def score(lv, p1, pred, pick=None):
             ops.eval_counters_rows(pred, tg, p1.view(-1), lv, *csr, self.acc)
             if self.report is not None:
                 ops.eval_report_rows(pred, tg, p1.view(-1), lv, *csr, self.report)
+            if pick is not None:
+                ops.hedge_counters_rows(pick, tg, csr[0], csr[1], self.hedge_tab)
         return score, [tg], lambda lv: lv
 
     def _join_tail(self) -> None:
@@ -165,18 +184,33 @@ class Evaluator:
         ptr, nodes, _ = self._ancestor_csr()
         return ops.path_scores(logits, ptr, nodes, self._wtab, out=self._scores[:rows * n].view(rows, n))
 
+    def hedge_picks(self, scores: torch.Tensor, mass_out: Optional[torch.Tensor] = None):
+        """hgr_subtree_hedge of ``scores`` [B, >= N] (what hgr_eval_rows gets) with this Evaluator's thresholds and temperature over
+        the test classes, into its pick buffers: (pick int32 [B, T], pick_mass fp32 [B, T]), valid until the next batch."""
+        assert self.hedge is not None, "Evaluator(model, hedge=(...)) keeps the thresholds"
+        rows, t = scores.shape[0], len(self.hedge)
+        if self._hedge_pick is None or self._hedge_pick[0].numel() < rows * t or self._hedge_pick[0].device != scores.device:
+            self._hedge_pick = (torch.empty(rows * t, dtype=torch.int32, device=scores.device),
+                                torch.empty(rows * t, dtype=torch.float32, device=scores.device))
+        ptr, nodes, _ = self._ancestor_csr()
+        pick, pmass = (b[:rows * t].view(rows, t) for b in self._hedge_pick)
+        return ops.subtree_hedge(scores, self.index.test_pos, ptr, nodes, self.hedge_temperature, self._hedge_thr, pick, pmass, mass_out)
+
     def _add_logits(self, logits: torch.Tensor, scorer, want_outputs: bool):
         score, _, view = scorer
         self._join_tail()
         if self.decode == "path":                      # path decoding IS hgr_eval_rows on the path scores
             logits = self.path_scores(logits)
         lv, p1, pred = ops.eval_rows(logits, self.index, max(TOPK))
-        score(lv, p1, pred)
+        if self.hedge is None:
+            score(lv, p1, pred)
+        else:                                          # the hedge reads the tensor hgr_eval_rows got: the two decodings compose
+            score(lv, p1, pred, self.hedge_picks(logits)[0])
         return (pred, view(lv)) if want_outputs else None
 
     def _add_images(self, imgs: torch.Tensor, scorer, want_outputs: bool):
         score, reads, view = scorer
-        if self.decode == "path":                     # the fused kernel never has the whole row: logits -> path scores -> hgr_eval_rows
+        if self.decode == "path" or self.hedge is not None:     # the fused kernel never has the whole row: logits -> (path scores, hedge) -> hgr_eval_rows
             return self._add_logits(self.model(imgs, None, static_output=True), scorer, want_outputs)
         plan = self._fused_plan()
         if not plan.supported:                        # a hierarchy beyond hgr_logits_eval's capacity: logits + hgr_eval_rows
@@ -213,8 +247,8 @@ class Evaluator:
 
     def fused_ok(self) -> bool:
         """hgr_logits_eval needs an embedding width that is a multiple of 128 (<= 1024) and <= 32 levels - and flat decoding: the path
-        scores of a column read other columns of its row, which the fused kernel never holds together."""
-        if self.decode == "path":
+        scores of a column read other columns of its row, which the fused kernel never holds together; so does the softmax of a hedge."""
+        if self.decode == "path" or self.hedge is not None:
             return False
         d = self.model._zsl16.shape[1] if self.model._zsl16 is not None else 0
         if not (d % 128 == 0 and 128 <= d <= 1024 and self.n_levels <= 32 and self.index.n_test >= max(TOPK)):
@@ -269,13 +303,25 @@ class Evaluator:
         """The hierarchy report's table as a CPU int64 tensor [ops.REPORT_LEN] (one D2H copy); with a process group the tables of
         all ranks are summed first - an int64 all-reduce, exact, on the device (nccl) as on CPU tensors (gloo)."""
         assert self.report is not None, "Evaluator(model, report=True) keeps the hierarchy report"
-        self._join_tail()                               # pipelined steps advance the table on the tail stream
-        table = self.report
+        return self._read_table(self.report, group)
+
+    def _read_table(self, table: torch.Tensor, group) -> torch.Tensor:
+        self._join_tail()                               # pipelined steps advance the tables on the tail stream
         if group is not None:
             import torch.distributed as dist
             table = table.clone()
             dist.all_reduce(table, op=dist.ReduceOp.SUM, group=group)
         return table.cpu()
+
+    def hedge_table(self, group=None) -> torch.Tensor:
+        """The hedge outcome table as a CPU int64 tensor [T, ops.HEDGE_COLS] (one D2H copy); with a process group summed over the
+        ranks first, through the int64 all-reduce of report_table."""
+        assert self.hedge_tab is not None, "Evaluator(model, hedge=(...)) keeps the hedge table"
+        return self._read_table(self.hedge_tab, group)
+
+    def hedge_dict(self, group=None) -> dict:
+        """The hedge outcomes as plain Python values (hedge_from_table), ready for json.dump."""
+        return hedge_from_table(self.hedge_table(group), self.hedge, temperature=self.hedge_temperature)
 
     def report_dict(self, group=None) -> dict:
         """The hierarchy report as plain Python values (report_from_table), ready for json.dump."""
@@ -346,16 +392,76 @@ def format_report(rep: dict) -> str:
     return "\n".join(lines)
 
 
+def hedge_from_table(table: torch.Tensor, thresholds, temperature: Optional[float] = None) -> dict:
+    """The table of hgr_hedge_counters_rows (CPU int64 [T, ops.HEDGE_COLS], layout in include/hgr.h) as plain Python values; a pure
+    function of the table.  Per threshold: the rows, the five outcomes as counts and as percentages of the rows (None without rows),
+    correct = abstain + exact + ancestor (a pick that names the target or something above it says nothing wrong), the mean pick depth
+    SUM_LPICK / ROWS (path length: 0 = abstained), hierarchical precision SUM_COMMON / SUM_LPICK (None when nothing was picked) and
+    recall SUM_COMMON / SUM_LT, and the histogram of the picks' path lengths with empty bins left out."""
+    thresholds = [float(t) for t in thresholds]
+    assert table.dtype == torch.int64 and tuple(table.shape) == (len(thresholds), ops.HEDGE_COLS) and not table.is_cuda
+    out = []
+    for theta, row in zip(thresholds, table.tolist()):
+        c = dict(zip(ops.HEDGE_COL_NAMES, row))
+        n = c["rows"]
+        e = {"threshold": theta, "rows": n}
+        for name in ("abstain", "exact", "ancestor", "below", "wrong"):
+            e[name] = c[name]
+            e[name + "_pct"] = c[name] / n * 100.0 if n else None
+        e["correct"] = c["abstain"] + c["exact"] + c["ancestor"]
+        e["correct_pct"] = e["correct"] / n * 100.0 if n else None
+        e["mean_pick_depth"] = c["sum_lpick"] / n if n else None
+        e["h_precision"] = c["sum_common"] / c["sum_lpick"] if c["sum_lpick"] else None
+        e["h_recall"] = c["sum_common"] / c["sum_lt"] if c["sum_lt"] else None
+        e["pick_depth_histogram"] = {str(d): v for d, v in enumerate(row[ops.HEDGE_COL_HIST:]) if v}
+        out.append(e)
+    rep = {"thresholds": thresholds, "by_threshold": out}
+    if temperature is not None:
+        rep["temperature"] = float(temperature)
+    return rep
+
+
+def format_hedge(rep: dict) -> str:
+    """One line per threshold: what evaluate.test prints behind the metric string."""
+    def f(v, spec):
+        return format(v, spec) if v is not None else "-".rjust(int(spec.split(".")[0]))
+    lines = ["hedge theta     rows  abstain(%)  exact(%)  ancestor(%)  below(%)  wrong(%)  correct(%)  depth  h_prec  h_rec"]
+    for e in rep["by_threshold"]:
+        lines.append("hedge {:5.3f} {:8d}  {}  {}  {}  {}  {}  {}  {}  {}  {}".format(
+            e["threshold"], e["rows"], f(e["abstain_pct"], "10.2f"), f(e["exact_pct"], "8.2f"), f(e["ancestor_pct"], "11.2f"),
+            f(e["below_pct"], "8.2f"), f(e["wrong_pct"], "8.2f"), f(e["correct_pct"], "10.2f"), f(e["mean_pick_depth"], "5.2f"),
+            f(e["h_precision"], "6.3f"), f(e["h_recall"], "5.3f")))
+    return "\n".join(lines)
+
+
+def parse_hedge(text):
+    """``--hedge 0.25,0.5,0.9`` -> (0.25, 0.5, 0.9); the values are checked by ops.hedge_thresholds."""
+    if text is None or isinstance(text, (tuple, list)):
+        return None if text is None else tuple(float(t) for t in text)
+    try:
+        th = tuple(float(t) for t in str(text).split(","))
+    except ValueError:
+        raise ValueError(f"--hedge {text!r}: comma-separated numbers") from None
+    ops.hedge_thresholds(th)
+    return th
+
+
 @torch.no_grad()
 def predict(model, imgs: torch.Tensor, k: int = max(TOPK), decode: str = "flat", decode_weights: str = "increasing",
-            want_scores: bool = False, evaluator: Optional[Evaluator] = None) -> Dict[str, torch.Tensor]:
+            want_scores: bool = False, evaluator: Optional[Evaluator] = None, hedge=None, hedge_temperature: Optional[float] = None,
+            want_mass: bool = False) -> Dict[str, torch.Tensor]:
     """Classify a batch of images (after ``model.update_classifier()``): {"topk": int32 [B, k] node ids among the test classes, best
     first, "top1": int32 [B] the best train class, "levels": int32 [B, n_levels] the best train class of every depth level (the
     reference's -1 filler competes, as in hgr_eval_rows)} - hgr_eval_rows on the logits (``decode="flat"``) or on their path scores (``"path"``, weights
     ``decode_weights``).  ``want_scores`` adds "scores": fp32 [B, N], what the predictions were taken from.  ``evaluator``: an
     Evaluator of this model to reuse (its index, weight table and scores buffer; its decode settings then hold) - without one, a
-    new one is built per call."""
-    ev = evaluator if evaluator is not None else Evaluator(model, decode=decode, decode_weights=decode_weights)
+    new one is built per call.  ``hedge`` (thresholds, with ``hedge_temperature``; or an ``evaluator`` built with them) adds "hedge":
+    int32 [B, T], per threshold the deepest node whose subtree holds that much of the row's probability among the test classes (-1: none
+    does), and "hedge_mass": fp32 [B, T], that node's mass; ``want_mass`` adds "mass": fp32 [B, N], every node's subtree mass."""
+    ev = evaluator if evaluator is not None else Evaluator(model, decode=decode, decode_weights=decode_weights, hedge=hedge,
+                                                           hedge_temperature=hedge_temperature)
+    if want_mass and ev.hedge is None:
+        raise ValueError("want_mass needs hedge thresholds")
     scores = model(imgs.to(model.train_index.device), None, static_output=True)
     if ev.decode == "path":
         scores = ev.path_scores(scores)
@@ -363,6 +469,12 @@ def predict(model, imgs: torch.Tensor, k: int = max(TOPK), decode: str = "flat",
     out = {"topk": topk, "top1": p1.view(-1), "levels": lv}
     if want_scores:
         out["scores"] = scores[:, :ev.index.n_nodes].clone()          # the logits / the scores buffer are reused by the next batch
+    if ev.hedge is not None:
+        mass = torch.empty((scores.shape[0], ev.index.n_nodes), dtype=torch.int32, device=scores.device) if want_mass else None
+        pick, pmass = ev.hedge_picks(scores, mass)
+        out["hedge"], out["hedge_mass"] = pick.clone(), pmass.clone()   # the pick buffers are reused by the next batch
+        if want_mass:
+            out["mass"] = mass.to(torch.float32) * (1.0 / ops.HEDGE_SCALE)
     return out
 
 
@@ -395,6 +507,9 @@ def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, gr
     kw = {"report": True} if report_path else {}
     if decode != "flat":
         kw.update(decode=decode, decode_weights=decode_weights)
+    hedge, hedge_path = parse_hedge(getattr(opts, "hedge", None)), getattr(opts, "hedge_report", None)
+    if hedge is not None:
+        kw.update(hedge=hedge, hedge_temperature=getattr(opts, "hedge_temperature", None))
     ev = Evaluator(model, **kw)
     fused = ev.fused_ok() and os.environ.get("HGR_EVAL_FUSED", "1") != "0"
     packed = bool(getattr(opts, "pack_batches", False))
@@ -430,6 +545,14 @@ def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, gr
             with open(report_path, "w") as f:
                 json.dump(rep, f, indent=1)
             print(format_report(rep), flush=True)
+    if hedge is not None:                                # behind the metric string, which stays as it is
+        rep = ev.hedge_dict(group)
+        import torch.distributed as dist
+        if group is None or dist.get_rank() == 0:
+            if hedge_path:
+                with open(hedge_path, "w") as f:
+                    json.dump(rep, f, indent=1)
+            print(format_hedge(rep), flush=True)
     if log:
         with open(model.save_path + "arugements.log", "a") as f:
             f.writelines(out + "\n")

@@ -17,7 +17,7 @@ import os
 import torch
 
 from . import synth
-from .evaluate import DECODE_WEIGHTS, DECODES, test
+from .evaluate import DECODE_WEIGHTS, DECODES, parse_hedge, test
 from .model import tree_model
 from .training import FusedAdamW
 from .utils import cosine_lr
@@ -85,6 +85,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "node scored by the weighted logits along its root-to-node path)")
     p.add_argument("--decode_weights", default="increasing", type=str, choices=list(DECODE_WEIGHTS),
                    help="--decode path: the weights along a path, top-most ancestor first (get_weights' methods; self = the node alone)")
+    p.add_argument("--hedge", default=None, type=parse_hedge, metavar="T1,T2,...",
+                   help="evaluation: hedged predictions (hgr_subtree_hedge) - per threshold, 1..8 increasing values in (0, 1], the deepest "
+                        "node whose subtree holds that much of the row's softmax over the test classes; outcomes are printed per threshold")
+    p.add_argument("--hedge_temperature", default=None, type=float, help="--hedge: the softmax's temperature (default: the model's logit scale)")
+    p.add_argument("--hedge_report", default=None, type=str, metavar="PATH", help="--hedge: also write the outcomes per threshold as JSON to PATH")
     p.add_argument("--ref_quirks", default=False, action="store_true",
                    help="reproduce the reference's missing zero_grad() (gradients accumulate across steps, SURVEY F11-i)")
     return p

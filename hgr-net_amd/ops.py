@@ -3,6 +3,7 @@ sizes and the current HIP stream to libhgr.so.  torch is plumbing here (device m
 all arithmetic happens in the hand-written kernels."""
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -611,6 +612,69 @@ def path_scores(logits: torch.Tensor, anc_ptr: torch.Tensor, anc_nodes: torch.Te
     _lib.call("hgr_path_scores", _dev(logits), logits.stride(0), _dev(out), out.stride(0), n_nodes, _dev(anc_ptr), _dev(anc_nodes),
               _dev(wtab), rows, _stream())
     return out[:, :n_nodes]
+
+
+# hedged predictions: mirrors HGR_HEDGE_* of include/hgr.h (columns of one row of the outcome table, in int64 entries)
+HEDGE_MAXT = 8
+HEDGE_MAXN = 36864
+HEDGE_SCALE = 1 << 30                                              # masses and thresholds are multiples of 2^-30
+HEDGE_COL_NAMES = ("rows", "abstain", "exact", "ancestor", "below", "wrong", "sum_lpick", "sum_common", "sum_lt")
+HEDGE_COL_HIST = len(HEDGE_COL_NAMES)                              # [33] picks by path length, 0 = abstained or without a path
+HEDGE_COLS = HEDGE_COL_HIST + REPORT_MAXL + 1                      # 42
+
+
+def hedge_thresholds(thetas) -> list:
+    """thr[i] = ceil(theta_i * 2^30), in double on the host: the fixed-point thresholds of hgr_subtree_hedge.  1 .. HEDGE_MAXT values
+    in (0, 1], strictly increasing; anything else is a ValueError."""
+    try:
+        th = [float(t) for t in thetas]
+    except TypeError:
+        raise ValueError(f"hedge thresholds {thetas!r}: a sequence of numbers") from None
+    if not 1 <= len(th) <= HEDGE_MAXT:
+        raise ValueError(f"hedge: {len(th)} thresholds (1..{HEDGE_MAXT})")
+    if not all(0.0 < t <= 1.0 for t in th):                        # a NaN fails both comparisons
+        raise ValueError(f"hedge thresholds {th}: each in (0, 1]")
+    if any(b <= a for a, b in zip(th, th[1:])):
+        raise ValueError(f"hedge thresholds {th}: strictly increasing")
+    return [int(math.ceil(t * HEDGE_SCALE)) for t in th]
+
+
+def subtree_hedge(scores: torch.Tensor, cand_pos: Optional[torch.Tensor], anc_ptr: torch.Tensor, anc_nodes: torch.Tensor,
+                  temperature: float, thr: torch.Tensor, pick: Optional[torch.Tensor] = None, pick_mass: Optional[torch.Tensor] = None,
+                  mass_out: Optional[torch.Tensor] = None):
+    """(pick int32 [rows, T], pick_mass fp32 [rows, T]) of hgr_subtree_hedge (definition in include/hgr.h): per threshold the deepest
+    node whose subtree holds at least that much of the row's softmax(temperature * scores) over the candidates (cand_pos[n] >= 0; None:
+    every node), -1 where no node does.  ``thr``: int32 [T] on the device, hedge_thresholds' values.  ``mass_out``: int32 [rows, >=
+    n_nodes] (unit column stride) that receives every node's mass in units of 2^-30 (below 2^31: int32 holds the uint32 as it is);
+    further columns are left alone.  ``scores`` may be a view of a wider buffer."""
+    n_nodes = anc_ptr.numel() - 1
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.stride(1) == 1
+    assert anc_ptr.dtype == anc_nodes.dtype == torch.int32 and anc_ptr.is_contiguous() and anc_nodes.is_contiguous()
+    assert cand_pos is None or (cand_pos.dtype == torch.int32 and cand_pos.is_contiguous() and cand_pos.numel() == n_nodes)
+    assert thr.dtype == torch.int32 and thr.dim() == 1 and thr.is_contiguous()
+    rows, t = scores.shape[0], thr.numel()
+    if pick is None:
+        pick = torch.empty((rows, t), dtype=torch.int32, device=scores.device)
+    if pick_mass is None:
+        pick_mass = torch.empty((rows, t), dtype=torch.float32, device=scores.device)
+    assert pick.dtype == torch.int32 and pick.shape == (rows, t) and pick.is_contiguous()
+    assert pick_mass.dtype == torch.float32 and pick_mass.shape == (rows, t) and pick_mass.is_contiguous()
+    assert mass_out is None or (mass_out.dim() == 2 and mass_out.dtype == torch.int32 and mass_out.stride(1) == 1 and mass_out.shape[0] == rows)
+    # sizes and the temperature go to the library as they are: it rejects what hgr.h lists, before anything is launched
+    _lib.call("hgr_subtree_hedge", _dev(scores), scores.stride(0), n_nodes, _dev(cand_pos), _dev(anc_ptr), _dev(anc_nodes), float(temperature),
+              _dev(thr), t, _dev(pick), _dev(pick_mass), _dev(mass_out), mass_out.stride(0) if mass_out is not None else 0, rows, _stream())
+    return pick, pick_mass
+
+
+def hedge_counters_rows(pick: torch.Tensor, targets: torch.Tensor, anc_ptr: torch.Tensor, anc_nodes: torch.Tensor, table: torch.Tensor) -> None:
+    """Add one batch of picks to the hedge outcome table, int64 [T, HEDGE_COLS] (hgr_hedge_counters_rows, include/hgr.h): the padding
+    rule of eval_counters_rows, exact integer counts only."""
+    assert pick.dtype == anc_ptr.dtype == anc_nodes.dtype == torch.int32 and pick.dim() == 2 and pick.is_contiguous()
+    assert anc_ptr.is_contiguous() and anc_nodes.is_contiguous() and anc_ptr.numel() >= 2
+    assert table.dtype == torch.int64 and table.shape == (pick.shape[1], HEDGE_COLS) and table.is_contiguous()
+    assert targets is not None and targets.dtype == torch.int64 and targets.is_contiguous() and targets.numel() == pick.shape[0]
+    _lib.call("hgr_hedge_counters_rows", _dev(pick), pick.shape[1], _dev(targets), _dev(anc_ptr), _dev(anc_nodes), anc_ptr.numel() - 1,
+              _dev(table), pick.shape[0], _stream())
 
 
 # ---- ModifiedResNet (RN) tower -------------------------------------------------------------------

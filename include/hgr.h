@@ -330,6 +330,50 @@ int hgr_eval_report_rows(const int32_t *pred, int k, const int64_t *targets, con
 int hgr_path_scores(const float *logits, int64_t ld, float *scores, int64_t ld_out, int n_nodes, const int32_t *anc_ptr,
                     const int32_t *anc_nodes, const float *wtab /* [33][32] */, int rows, void *stream);
 
+/* Hedged predictions: the softmax of a class row in 2^-30 fixed point, every node's subtree mass, and per threshold the deepest node
+ * whose mass reaches it.  scores fp32 [rows, ld], ld >= n_nodes; cand_pos int32 [n_nodes]: an entry >= 0 marks a candidate, a null
+ * pointer makes every node one; anc_ptr / anc_nodes: the CSR of hgr_eval_counters_rows, P(n) = anc_nodes[anc_ptr[n] : anc_ptr[n + 1]]
+ * (ancestors from the top down, then n), L(n) its length; temperature tau > 0; thr uint32 [n_thr] on the device, 1 <= n_thr <=
+ * HGR_HEDGE_MAXT: thresholds in fixed point, thr[i] = ceil(theta_i * 2^30) made on the host in double, theta in (0, 1].  Outputs:
+ * pick int32 [rows, n_thr], pick_mass fp32 [rows, n_thr], and optionally mass_out uint32 [rows, ld_mass].  For row r:
+ *   m      = max of x[r, n] over the candidates
+ *   e[n]   = exp(tau * (x[r, n] - m)) in fp32 (one rounding each for the difference, the product and expf)
+ *   Z      = sum of e over the candidates in fp32, in an order fixed for a build and the same for every row, whatever the batch
+ *   q[n]   = (uint32) rint(e[n] / Z * 2^30) for candidates, 0 for every other node
+ *   mass   : a candidate n with 1 <= L(n) <= 32 adds q[n] to mass[a] for every a = P(n)[j] with (unsigned)a < n_nodes;
+ *            a candidate with L(n) outside 1..32 adds q[n] to mass[n] only
+ *   mass[a] is a uint32 sum: with 2^30 as the scale a row's total stays below 2^31, integer adds commute - given q, the masses
+ *   depend on no order, lane or launch (the reason the counters and the report keep integers)
+ *   pick[r, i]      = among the nodes a with 1 <= L(a) <= 32 and mass[a] >= thr[i]: the largest L(a), then the largest mass[a], then
+ *                     the smallest id; pick_mass[r, i] = mass[a] * 2^-30
+ *                     no such node: pick = -1 (abstain, "root"), pick_mass = (sum of q) * 2^-30
+ *   mass_out[r, :n_nodes] = mass, if requested (columns n_nodes .. ld_mass - 1 are not written)
+ *   a row without a candidate: pick = -1, pick_mass = 0, mass all zero
+ * Rejected before anything is launched: a null required operand, rows < 1, n_nodes < 1, n_nodes > HGR_HEDGE_MAXN, ld < n_nodes,
+ * ld_mass < n_nodes with mass_out, n_thr outside 1..8, temperature <= 0 or not finite.  One workgroup of 1024 threads per row (a
+ * capped grid loops over rows) with the mass row in LDS as uint32[n_nodes]: HGR_HEDGE_MAXN * 4 = 147 456 B of the 160 KiB a gfx950
+ * workgroup may own.  Passes over the row: maximum, normaliser, scatter (one candidate per lane up its path, LDS atomic adds, q == 0
+ * skipped), then one pass over LDS that keeps per threshold the largest key L << 47 | mass << 16 | (0xFFFF - id). */
+#define HGR_HEDGE_MAXT 8
+#define HGR_HEDGE_MAXN 36864
+int hgr_subtree_hedge(const float *scores, int64_t ld, int n_nodes, const int32_t *cand_pos, const int32_t *anc_ptr,
+                      const int32_t *anc_nodes, float temperature, const uint32_t *thr, int n_thr, int32_t *pick, float *pick_mass,
+                      uint32_t *mass_out, int64_t ld_mass, int rows, void *stream);
+
+/* What became of the picks: pick int32 [rows, n_thr] against targets int64 [rows], added into an int64 table [n_thr][HGR_HEDGE_COLS]
+ * on the device - exact integer counts only (64-bit atomics; per-launch counts in LDS, one flush per block), so the table depends
+ * neither on the order of the rows nor on the cut into launches.  A row is padding (counts nothing) exactly when it is padding for
+ * hgr_eval_counters_rows: target outside [0, n_nodes) or Lt outside 1..32 - ROWS equals the counters' num_sample.  With x the pick, Lx
+ * its path length and c = c(x, t) the common-prefix length of the report (an abstention x == -1: Lx = 0, c = 0; any other pick
+ * outside [0, n_nodes) or with Lx outside 1..32: Lx = 0, c = 0, WRONG), every non-padding row adds 1 to ROWS, 1 to exactly one of
+ *   ABSTAIN (x == -1), EXACT (x == t), ANCESTOR (c == Lx < Lt), BELOW (c == Lt < Lx), WRONG (everything else),
+ * Lx to SUM_LPICK, c to SUM_COMMON, Lt to SUM_LT, and 1 to HIST[Lx] (bins 0..32). */
+enum { HGR_HEDGE_COL_ROWS = 0, HGR_HEDGE_COL_ABSTAIN = 1, HGR_HEDGE_COL_EXACT = 2, HGR_HEDGE_COL_ANCESTOR = 3, HGR_HEDGE_COL_BELOW = 4,
+       HGR_HEDGE_COL_WRONG = 5, HGR_HEDGE_COL_SUM_LPICK = 6, HGR_HEDGE_COL_SUM_COMMON = 7, HGR_HEDGE_COL_SUM_LT = 8, HGR_HEDGE_COL_HIST = 9 };
+#define HGR_HEDGE_COLS (HGR_HEDGE_COL_HIST + HGR_REPORT_MAXL + 1)                                  /* 42 */
+int hgr_hedge_counters_rows(const int32_t *pick, int n_thr, const int64_t *targets, const int32_t *anc_ptr, const int32_t *anc_nodes,
+                            int n_nodes, int64_t *table /* [n_thr][HGR_HEDGE_COLS] */, int rows, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * ModifiedResNet (RN50) tower, clip/model.py:93-150.  Activations are NHWC 16-bit ([B, H, W, C] =
  * a row-major [B*H*W, C] matrix), so every 1x1 convolution IS hgr_gemm_nt; inference BatchNorm
