@@ -191,6 +191,24 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {      // two 32-bit shuffles per step
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
+        const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+// ---- orderable keys: the evaluation's order "larger value, then lower subset position" as ONE unsigned compare ----------------------
+// orderable(): the float's bits mapped so that unsigned order == float order (-inf -> 0x007FFFFF: every real key is > 0, 0 = "empty").
+// key_of(v, p) = (orderable(v) << 32) | (INT_MAX - p): unsigned max == larger value, then smaller position.  Written by the tile stage of
+// hgr_logits_eval (hgr_logits_slab.hip) and by eval_rows_lds, read back with key_decode() by the row kernels of hgr_select.hip.
+__device__ __forceinline__ unsigned orderable(float v) { const unsigned u = __float_as_uint(v); return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+__device__ __forceinline__ float unorderable(unsigned u) { return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+__device__ __forceinline__ unsigned long long key_of(float v, int p) { return ((unsigned long long)orderable(v) << 32) | (unsigned)(0x7fffffff - p); }
+__device__ __forceinline__ void key_decode(unsigned long long m, float &v, int &p) { v = unorderable((unsigned)(m >> 32)); p = 0x7fffffff - (int)(unsigned)m; }
 
 // sum over the 16 lanes of a DPP row (lanes with equal lane >> 4), result in every lane of the row; fixed order.
 // Must be executed by all lanes of the wave's rows it concerns (no divergence inside a row).

@@ -215,10 +215,9 @@ __global__ __launch_bounds__(LS_NT) void logits_slab(SlabArgs p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) P = min(P, (tp[2 * s + jj][e] >= 0 && tv[jj][e] == V) ? tp[2 * s + jj][e] : 0x7fffffff);
             P = xmini(P);
-            const unsigned vu = __float_as_uint(V);
             // (no train column in the slice: P stays INT_MAX -> key 0, which loses against every real key)
-            const unsigned long long key = P == 0x7fffffff ? 0ull
-                : ((unsigned long long)(vu ^ ((vu >> 31) ? 0xFFFFFFFFu : 0x80000000u)) << 32) | (unsigned)(0x7fffffff - P);
+            const unsigned long long vkey = key_of(V, P);                   // formed ahead of the select, as the kernel always did: same code
+            const unsigned long long key = P == 0x7fffffff ? 0ull : vkey;
             // ---- test columns: per 16-column group the largest value, the position of an element attaining it, the runner-up ----
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {

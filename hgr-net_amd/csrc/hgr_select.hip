@@ -1,15 +1,23 @@
 // Selection over the logits rows: top-k over a column subset (main.py:136-139,157) and the
 // level-segmented arg-max of the hierarchy metrics (main.py:162-176).  Index work: results are
 // defined bit-exactly (largest value first, ties to the lowest subset position).
+// Five kernels: topk_rows and level_argmax (unfused, kept as independent checks), eval_rows (register accumulators, 17 - 32 levels),
+// eval_rows_lds (<= 16 levels) and logits_eval_rows (row stage of hgr_logits_eval).  The order, the filler rule, the threshold, the
+// ranking and the fallback rounds exist once, in the helpers below; the 64-bit key of the order is in hgr_common.h.
 #include "hgr_common.h"
-#include <stdlib.h>
 #include <math.h>
 
 namespace {
 
-struct Best { float v; int p; };
+struct Best { float v; int p; };                            // empty: (-inf, INT_MAX)
 
 __device__ __forceinline__ bool better(float v, int p, float bv, int bp) { return v > bv || (v == bv && p < bp); }
+
+__device__ __forceinline__ Best best_of_key(unsigned long long m) {      // key_of()'s inverse; 0 = empty
+    Best b = {-INFINITY, 0x7fffffff};
+    if (m) key_decode(m, b.v, b.p);
+    return b;
+}
 
 __device__ __forceinline__ Best wave_best(Best b) {
 #pragma unroll
@@ -19,6 +27,72 @@ __device__ __forceinline__ Best wave_best(Best b) {
         if (better(ov, op, b.v, b.p)) { b.v = ov; b.p = op; }
     }
     return b;
+}
+
+// best of a block of NW waves, returned to every thread; s_v / s_p: NW LDS slots (the leading barrier protects their previous readers)
+template <int NW>
+__device__ __forceinline__ Best block_best(Best b, float *s_v, int *s_p, int tid) {
+    const Best w = wave_best(b);
+    __syncthreads();
+    if ((tid & 63) == 0) { s_v[tid >> 6] = w.v; s_p[tid >> 6] = w.p; }
+    __syncthreads();
+    Best r = {s_v[0], s_p[0]};
+    for (int i = 1; i < NW; ++i)
+        if (better(s_v[i], s_p[i], r.v, r.p)) { r.v = s_v[i]; r.p = s_p[i]; }
+    return r;
+}
+
+// The reference fills every train column outside level l with -1 before its arg-max (main.py:170-173), so the filler competes: b = best
+// (value, train position) inside the level, fo = first train position outside it (-1: none).  Returns the winning train position.
+__device__ __forceinline__ int level_winner(Best b, int fo, int n_train) {
+    const bool has_c = b.p < n_train, has_f = fo >= 0;
+    if (has_c && (!has_f || b.v > -1.0f || (b.v == -1.0f && b.p < fo))) return b.p;
+    return has_f ? fo : b.p;
+}
+
+// Top-k threshold of the eval_rows kernels (threads tid < 256, between two barriers): the k-th best of the 256 slice maxima.  k distinct
+// elements >= t are guaranteed only if at least k slices are non-empty (clustered / tiny test sets can put several test columns into one
+// slice); otherwise every test element is a candidate.
+__device__ __forceinline__ void slice_threshold(const float *s_mv, const int *s_mp, int k, int tid, float &s_t, int &s_tp) {
+    if (tid < 256) {
+        const float mv = s_mv[tid]; const int mp = s_mp[tid];
+        int rank = 0, nonempty = 0;
+        for (int j = 0; j < 256; ++j) { rank += better(s_mv[j], s_mp[j], mv, mp) ? 1 : 0; nonempty += s_mp[j] != 0x7fffffff ? 1 : 0; }
+        if (nonempty < k) { if (tid == 0) { s_t = -INFINITY; s_tp = 0x7fffffff; } }
+        else if (rank == k - 1) { s_t = mv; s_tp = mp; }
+    }
+}
+
+// rank the cnt candidates by brute-force comparison; emit(rank, value, position) for ranks < k
+template <int NT, typename F>
+__device__ __forceinline__ void rank_and_emit(const float *s_cv, const int *s_cp, int cnt, int k, int tid, F emit) {
+    for (int c = tid; c < cnt; c += NT) {
+        const float v = s_cv[c]; const int p = s_cp[c];
+        int rk = 0;
+        for (int j = 0; j < cnt; ++j) rk += better(s_cv[j], s_cp[j], v, p) ? 1 : 0;
+        if (rk < k) emit(rk, v, p);
+    }
+}
+
+// Candidate-list overflow of the eval_rows kernels (heavily duplicated data): k rounds of block arg-max over the row's test columns; an
+// element is "removed" by requiring it to be worse than the previous winner in (value, position) order, so nothing has to be written back
+template <int NT>
+__device__ __forceinline__ void topk_rounds(const float *lr, int n_nodes, const int32_t *test_pos, const int32_t *test_cols, int n_test, int k,
+                                            int32_t *out, float *s_v, int *s_p, int tid) {
+    Best last = {INFINITY, -1};
+    for (int j = 0; j < k; ++j) {
+        Best b = {-INFINITY, 0x7fffffff};
+        for (int c = tid; c < n_nodes; c += NT) {
+            const int te = test_pos[c];
+            if (te < 0) continue;
+            const float v = lr[c] + 0.0f;
+            if (better(last.v, last.p, v, te) && better(v, te, b.v, b.p)) { b.v = v; b.p = te; }
+        }
+        b = block_best<NT / 64>(b, s_v, s_p, tid);
+        if (tid == 0) out[j] = b.p < n_test ? test_cols[b.p] : -1;
+        last = b;
+        __syncthreads();
+    }
 }
 
 // One workgroup per row; the row's subset is staged once in LDS (<= 40000 floats).
@@ -41,8 +115,8 @@ __global__ __launch_bounds__(256) void topk_rows(const float *__restrict__ logit
     __shared__ float s_cv[TOPK_CAND];
     __shared__ int s_cp[TOPK_CAND];
     __shared__ float s_t;
-    __shared__ int s_tp, s_cnt, s_win;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int s_tp, s_cnt;
+    const int tid = threadIdx.x;
     const int row = blockIdx.x;
     const float *lr = logits + (int64_t)row * ld;
     Best mine = {-INFINITY, 0x7fffffff};
@@ -74,15 +148,10 @@ __global__ __launch_bounds__(256) void topk_rows(const float *__restrict__ logit
     __syncthreads();
     const int cnt = s_cnt;
     if (cnt <= TOPK_CAND) {
-        for (int c = tid; c < cnt; c += 256) {
-            const float v = s_cv[c]; const int p = s_cp[c];
-            int rk = 0;
-            for (int j = 0; j < cnt; ++j) rk += better(s_cv[j], s_cp[j], v, p) ? 1 : 0;
-            if (rk < k) {
-                out_idx[(int64_t)row * k + rk] = cols ? cols[p] : p;
-                if (out_val) out_val[(int64_t)row * k + rk] = v;
-            }
-        }
+        rank_and_emit<256>(s_cv, s_cp, cnt, k, tid, [&](int rk, float v, int p) {
+            out_idx[(int64_t)row * k + rk] = cols ? cols[p] : p;
+            if (out_val) out_val[(int64_t)row * k + rk] = v;
+        });
         return;
     }
     // fallback: k rounds of block arg-max with removal
@@ -95,23 +164,15 @@ __global__ __launch_bounds__(256) void topk_rows(const float *__restrict__ logit
         return b;
     };
     for (int j = 0; j < k; ++j) {
-        const Best w = wave_best(mine);
-        if (lane == 0) { s_mv[wave] = w.v; s_mp[wave] = w.p; }
-        __syncthreads();
+        const Best b = block_best<4>(mine, s_mv, s_mp, tid);
         if (tid == 0) {
-            Best b = {s_mv[0], s_mp[0]};
-#pragma unroll
-            for (int i = 1; i < 4; ++i)
-                if (better(s_mv[i], s_mp[i], b.v, b.p)) { b.v = s_mv[i]; b.p = s_mp[i]; }
-            s_win = b.p;
             const bool ok = b.p < n_cols;
             out_idx[(int64_t)row * k + j] = ok ? (cols ? cols[b.p] : b.p) : -1;
             if (out_val) out_val[(int64_t)row * k + j] = b.v;
             if (ok) vals[b.p] = -INFINITY;
         }
         __syncthreads();
-        if (mine.p == s_win) mine = scan();
-        __syncthreads();
+        if (mine.p == b.p) mine = scan();
     }
 }
 
@@ -171,11 +232,8 @@ __global__ __launch_bounds__(256) void level_argmax(const float *__restrict__ lo
         for (int i = 1; i < 4; ++i)
             if (better(s_v[i][l], s_p[i][l], b.v, b.p)) { b.v = s_v[i][l]; b.p = s_p[i][l]; }
         const int fdd = min(min(s_fd[0], s_fd[1]), min(s_fd[2], s_fd[3]));
-        const int fo = (l != lvl0) ? 0 : fdd;           // first filler position (may not exist)
-        int win;
-        const bool has_c = b.p < n_cols, has_f = fo < n_cols;
-        if (has_c && (!has_f || b.v > -1.0f || (b.v == -1.0f && b.p < fo))) win = b.p;
-        else win = has_f ? fo : b.p;
+        const int fo = (l != lvl0) ? 0 : fdd;           // first filler position (INT_MAX: none - level_winner() wants -1)
+        const int win = level_winner(b, fo < n_cols ? fo : -1, n_cols);
         out[(int64_t)row * n_levels + l] = cols ? cols[win] : win;
         s_bv[l] = b.v; s_bp[l] = b.p;
     }
@@ -196,7 +254,7 @@ __global__ __launch_bounds__(256) void level_argmax(const float *__restrict__ lo
 // One workgroup per row, tiny LDS footprint (8 workgroups per CU hide the load latency), the row (<= 160 KB) stays
 // L2-resident between its three sweeps:
 //   * level-segmented arg-max: ONE coalesced sweep over the row; every thread keeps the running best (value, position)
-//     of every depth level in registers (statically unrolled over <= 16 / 32 levels), then one wave-shuffle reduction per
+//     of every depth level in registers (statically unrolled over 32 levels), then one wave-shuffle reduction per
 //     level and 4 partials through LDS.  (Measured alternatives: a row staged in LDS + CSR walk of the levels is bound by
 //     one workgroup per CU and the index loads' latency, 175 us; folding into 12 LDS atomicMax slots serialises in the
 //     per-CU LDS atomic unit, 160 us.)
@@ -209,25 +267,14 @@ __global__ __launch_bounds__(256) void level_argmax(const float *__restrict__ lo
 // competes (main.py:170-173).
 constexpr int EV_NT = 1024;                 // threads per row: 16 waves, so 512 rows keep 8 waves per SIMD busy chip-wide
 constexpr int EV_NW = EV_NT / 64;
+constexpr int EV_NLV = 32;                     // level accumulators per thread (hgr_eval_rows takes <= 16 levels to eval_rows_lds)
 
-__device__ __forceinline__ Best block_best16(Best b, float *s_v, int *s_p, int tid) {
-    const Best w = wave_best(b);
-    __syncthreads();
-    if ((tid & 63) == 0) { s_v[tid >> 6] = w.v; s_p[tid >> 6] = w.p; }
-    __syncthreads();
-    Best r = {s_v[0], s_p[0]};
-    for (int i = 1; i < EV_NW; ++i)
-        if (better(s_v[i], s_p[i], r.v, r.p)) { r.v = s_v[i]; r.p = s_p[i]; }
-    return r;
-}
-
-template <int NLV>
 __global__ __launch_bounds__(EV_NT) void eval_rows(const float *__restrict__ logits, int64_t ld, int n_nodes, const unsigned char *__restrict__ lvl8,
                                                  const int32_t *__restrict__ train_pos, const int32_t *__restrict__ train_cols, int n_train, int n_levels,
                                                  const int32_t *__restrict__ filler_pos, const int32_t *__restrict__ test_pos, const int32_t *__restrict__ test_cols,
                                                  int n_test, int k, int32_t *__restrict__ out_level, int32_t *__restrict__ out_top1, int32_t *__restrict__ out_topk) {
-    __shared__ float s_lv[EV_NW][NLV];
-    __shared__ int s_lp[EV_NW][NLV];
+    __shared__ float s_lv[EV_NW][EV_NLV];
+    __shared__ int s_lp[EV_NW][EV_NLV];
     __shared__ float s_v[EV_NW];
     __shared__ int s_p[EV_NW];
     __shared__ float s_mv[256];
@@ -242,17 +289,17 @@ __global__ __launch_bounds__(EV_NT) void eval_rows(const float *__restrict__ log
     if (tid == 0) s_cnt = 0;
     // sweep 1 (coalesced over the columns): per-thread running best of every level (registers, statically unrolled) and
     // this thread's best test element
-    float bv[NLV];
-    int bp[NLV];
+    float bv[EV_NLV];
+    int bp[EV_NLV];
 #pragma unroll
-    for (int l = 0; l < NLV; ++l) { bv[l] = -INFINITY; bp[l] = 0x7fffffff; }
+    for (int l = 0; l < EV_NLV; ++l) { bv[l] = -INFINITY; bp[l] = 0x7fffffff; }
     Best mine = {-INFINITY, 0x7fffffff};
     for (int c = tid; c < n_nodes; c += EV_NT) {
         const float v = lr[c] + 0.0f;
         const int tp = train_pos[c];
         const int lv = tp >= 0 ? (int)lvl8[c] : -1;
 #pragma unroll
-        for (int l = 0; l < NLV; ++l)
+        for (int l = 0; l < EV_NLV; ++l)
             if (lv == l && better(v, tp, bv[l], bp[l])) { bv[l] = v; bp[l] = tp; }
         if (k > 0) {
             const int te = test_pos[c];
@@ -260,7 +307,7 @@ __global__ __launch_bounds__(EV_NT) void eval_rows(const float *__restrict__ log
         }
     }
 #pragma unroll
-    for (int l = 0; l < NLV; ++l) {
+    for (int l = 0; l < EV_NLV; ++l) {
         Best b = {bv[l], bp[l]};
         b = wave_best(b);
         if (lane == 0) { s_lv[wave][l] = b.v; s_lp[wave][l] = b.p; }
@@ -284,27 +331,14 @@ __global__ __launch_bounds__(EV_NT) void eval_rows(const float *__restrict__ log
             b = Best{s_lv[0][l], s_lp[0][l]};
             for (int i = 1; i < EV_NW; ++i)
                 if (better(s_lv[i][l], s_lp[i][l], b.v, b.p)) { b.v = s_lv[i][l]; b.p = s_lp[i][l]; }
-            const int fo = filler_pos[l];
-            const bool has_c = b.p < n_train, has_f = fo >= 0;
-            int win;
-            if (has_c && (!has_f || b.v > -1.0f || (b.v == -1.0f && b.p < fo))) win = b.p;
-            else win = has_f ? fo : b.p;
-            out_level[(int64_t)r * n_levels + l] = train_cols[win];
+            out_level[(int64_t)r * n_levels + l] = train_cols[level_winner(b, filler_pos[l], n_train)];
         }
         const Best top = wave_best(b);                      // unmasked top-1 = best of the level bests
         if (lane == 0 && out_top1) out_top1[r] = top.p < n_train ? train_cols[top.p] : -1;
     }
     if (k <= 0) return;
     // top-k over the test subset: threshold = k-th best of the 256 slice maxima, then sweep 2 collects the candidates
-    if (tid < 256) {
-        const float mv = s_mv[tid]; const int mp = s_mp[tid];
-        int rank = 0, nonempty = 0;
-        for (int j = 0; j < 256; ++j) { rank += better(s_mv[j], s_mp[j], mv, mp) ? 1 : 0; nonempty += s_mp[j] != 0x7fffffff ? 1 : 0; }
-        // k distinct elements >= t are guaranteed only if at least k slices are non-empty (clustered / tiny test sets can
-        // put several test columns into one slice); otherwise every test element is a candidate
-        if (nonempty < k) { if (tid == 0) { s_t = -INFINITY; s_tp = 0x7fffffff; } }
-        else if (rank == k - 1) { s_t = mv; s_tp = mp; }
-    }
+    slice_threshold(s_mv, s_mp, k, tid, s_t, s_tp);
     __syncthreads();
     const float t = s_t; const int tp0 = s_tp;
     for (int c = tid; c < n_nodes; c += EV_NT) {
@@ -318,47 +352,14 @@ __global__ __launch_bounds__(EV_NT) void eval_rows(const float *__restrict__ log
     }
     __syncthreads();
     const int cnt = s_cnt;
-    if (cnt <= TOPK_CAND) {
-        for (int c = tid; c < cnt; c += EV_NT) {
-            const float v = s_cv[c]; const int p = s_cp[c];
-            int rk = 0;
-            for (int j = 0; j < cnt; ++j) rk += better(s_cv[j], s_cp[j], v, p) ? 1 : 0;
-            if (rk < k) out_topk[(int64_t)r * k + rk] = test_cols[p];
-        }
-    } else {
-        // heavily duplicated data: k rounds of block arg-max; an element is "removed" by requiring it to be worse than the
-        // previous winner in (value, position) order, so nothing has to be written back
-        Best last = {INFINITY, -1};
-        for (int j = 0; j < k; ++j) {
-            Best b = {-INFINITY, 0x7fffffff};
-            for (int c = tid; c < n_nodes; c += EV_NT) {
-                const int te = test_pos[c];
-                if (te < 0) continue;
-                const float v = lr[c] + 0.0f;
-                if (better(last.v, last.p, v, te) && better(v, te, b.v, b.p)) { b.v = v; b.p = te; }
-            }
-            b = block_best16(b, s_v, s_p, tid);
-            if (tid == 0) out_topk[(int64_t)r * k + j] = b.p < n_test ? test_cols[b.p] : -1;
-            last = b;
-            __syncthreads();
-        }
-    }
+    int32_t *out = out_topk + (int64_t)r * k;
+    if (cnt <= TOPK_CAND) rank_and_emit<EV_NT>(s_cv, s_cp, cnt, k, tid, [&](int rk, float, int p) { out[rk] = test_cols[p]; });
+    else topk_rounds<EV_NT>(lr, n_nodes, test_pos, test_cols, n_test, k, out, s_v, s_p, tid);
 }
 
 // ---- same contract, LDS-private accumulators (n_levels <= 16) -----------------------------------------------------------
 constexpr int EL_NT = 512, EL_NW = EL_NT / 64, EL_NLV = 16;
 constexpr int EL_U = 8;                 // columns per thread per trip of the two sweeps
-
-__device__ __forceinline__ Best block_best8(Best b, float *s_v, int *s_p, int tid) {
-    const Best w = wave_best(b);
-    __syncthreads();
-    if ((tid & 63) == 0) { s_v[tid >> 6] = w.v; s_p[tid >> 6] = w.p; }
-    __syncthreads();
-    Best r = {s_v[0], s_p[0]};
-    for (int i = 1; i < EL_NW; ++i)
-        if (better(s_v[i], s_p[i], r.v, r.p)) { r.v = s_v[i]; r.p = s_p[i]; }
-    return r;
-}
 
 __global__ __launch_bounds__(EL_NT) void eval_rows_lds(const float *__restrict__ logits, int64_t ld, int n_nodes, const unsigned char *__restrict__ lvl8,
                                                  const int32_t *__restrict__ train_pos, const int32_t *__restrict__ train_cols, int n_train, int n_levels,
@@ -380,8 +381,7 @@ __global__ __launch_bounds__(EL_NT) void eval_rows_lds(const float *__restrict__
     if (tid == 0) s_cnt = 0;
     // sweep 1 (coalesced over the columns): a column belongs to ONE level, so instead of a 16-way compare chain over register
     // accumulators each thread keeps its per-level bests in its own LDS column (dynamic index = the level): one 8-byte
-    // read, one 64-bit compare and a rare write per column.  key = (orderable(value) << 32) | (0x7fffffff - position):
-    // unsigned max == "larger value, then smaller position"; 0 = empty.
+    // read, one 64-bit compare and a rare write per column (key_of(), hgr_common.h; 0 = empty).
 #pragma unroll
     for (int l = 0; l < EL_NLV; ++l) acc[l][tid] = 0ull;
     Best mine = {-INFINITY, 0x7fffffff};
@@ -400,8 +400,7 @@ __global__ __launch_bounds__(EL_NT) void eval_rows_lds(const float *__restrict__
             const float v = v4[u4] + 0.0f;
             const int tp = tp4[u4];
             if (tp >= 0 && lv4[u4] < EL_NLV) {                  // the level test is always true for a valid index (depth < n_levels <= 16)
-                const unsigned u = __float_as_uint(v);
-                const unsigned long long key = ((unsigned long long)(u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u)) << 32) | (unsigned)(0x7fffffff - tp);
+                const unsigned long long key = key_of(v, tp);
                 unsigned long long *slot = &acc[lv4[u4]][tid];
                 if (key > *slot) *slot = key;
             }
@@ -425,12 +424,7 @@ __global__ __launch_bounds__(EL_NT) void eval_rows_lds(const float *__restrict__
         unsigned long long m = 0ull;
 #pragma unroll
         for (int i = 0; i < EL_NT / 64; ++i) { const unsigned long long x = acc[l][lane + 64 * i]; m = x > m ? x : m; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned hi = __shfl_xor((unsigned)(m >> 32), o), lo = __shfl_xor((unsigned)m, o);
-            const unsigned long long x = ((unsigned long long)hi << 32) | lo;
-            m = x > m ? x : m;
-        }
+        m = wave_max_u64(m);
         if (lane == 0) s_key[l] = m;
     }
     __syncthreads();
@@ -438,33 +432,15 @@ __global__ __launch_bounds__(EL_NT) void eval_rows_lds(const float *__restrict__
         const int l = lane;
         Best b = {-INFINITY, 0x7fffffff};
         if (l < n_levels) {
-            const unsigned long long m = l < EL_NLV ? s_key[l] : 0ull;
-            if (m) {
-                const unsigned u = (unsigned)(m >> 32);
-                b.v = __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-                b.p = 0x7fffffff - (int)(unsigned)m;
-            }
-            const int fo = filler_pos[l];
-            const bool has_c = b.p < n_train, has_f = fo >= 0;
-            int win;
-            if (has_c && (!has_f || b.v > -1.0f || (b.v == -1.0f && b.p < fo))) win = b.p;
-            else win = has_f ? fo : b.p;
-            out_level[(int64_t)r * n_levels + l] = train_cols[win];
+            b = best_of_key(l < EL_NLV ? s_key[l] : 0ull);
+            out_level[(int64_t)r * n_levels + l] = train_cols[level_winner(b, filler_pos[l], n_train)];
         }
         const Best top = wave_best(b);                      // unmasked top-1 = best of the level bests
         if (lane == 0 && out_top1) out_top1[r] = top.p < n_train ? train_cols[top.p] : -1;
     }
     if (k <= 0) return;
     // top-k over the test subset: threshold = k-th best of the 256 slice maxima, then sweep 2 collects the candidates
-    if (tid < 256) {
-        const float mv = s_mv[tid]; const int mp = s_mp[tid];
-        int rank = 0, nonempty = 0;
-        for (int j = 0; j < 256; ++j) { rank += better(s_mv[j], s_mp[j], mv, mp) ? 1 : 0; nonempty += s_mp[j] != 0x7fffffff ? 1 : 0; }
-        // k distinct elements >= t are guaranteed only if at least k slices are non-empty (clustered / tiny test sets can
-        // put several test columns into one slice); otherwise every test element is a candidate
-        if (nonempty < k) { if (tid == 0) { s_t = -INFINITY; s_tp = 0x7fffffff; } }
-        else if (rank == k - 1) { s_t = mv; s_tp = mp; }
-    }
+    slice_threshold(s_mv, s_mp, k, tid, s_t, s_tp);
     __syncthreads();
     const float t = s_t; const int tp0 = s_tp;
     for (int c0 = tid; c0 < n_nodes; c0 += EL_U * EL_NT) {
@@ -487,31 +463,9 @@ __global__ __launch_bounds__(EL_NT) void eval_rows_lds(const float *__restrict__
     }
     __syncthreads();
     const int cnt = s_cnt;
-    if (cnt <= TOPK_CAND) {
-        for (int c = tid; c < cnt; c += EL_NT) {
-            const float v = s_cv[c]; const int p = s_cp[c];
-            int rk = 0;
-            for (int j = 0; j < cnt; ++j) rk += better(s_cv[j], s_cp[j], v, p) ? 1 : 0;
-            if (rk < k) out_topk[(int64_t)r * k + rk] = test_cols[p];
-        }
-    } else {
-        // heavily duplicated data: k rounds of block arg-max; an element is "removed" by requiring it to be worse than the
-        // previous winner in (value, position) order, so nothing has to be written back
-        Best last = {INFINITY, -1};
-        for (int j = 0; j < k; ++j) {
-            Best b = {-INFINITY, 0x7fffffff};
-            for (int c = tid; c < n_nodes; c += EL_NT) {
-                const int te = test_pos[c];
-                if (te < 0) continue;
-                const float v = lr[c] + 0.0f;
-                if (better(last.v, last.p, v, te) && better(v, te, b.v, b.p)) { b.v = v; b.p = te; }
-            }
-            b = block_best8(b, s_v, s_p, tid);
-            if (tid == 0) out_topk[(int64_t)r * k + j] = b.p < n_test ? test_cols[b.p] : -1;
-            last = b;
-            __syncthreads();
-        }
-    }
+    int32_t *out = out_topk + (int64_t)r * k;
+    if (cnt <= TOPK_CAND) rank_and_emit<EL_NT>(s_cv, s_cp, cnt, k, tid, [&](int rk, float, int p) { out[rk] = test_cols[p]; });
+    else topk_rounds<EL_NT>(lr, n_nodes, test_pos, test_cols, n_test, k, out, s_v, s_p, tid);
 }
 
 
@@ -602,8 +556,7 @@ __global__ __launch_bounds__(LE_NT, 4) void logits_eval_rows(const void *__restr
 #pragma unroll
         for (int i = 0; i < LE_MAXS / 64; ++i) {
             const int s = i * 64 + lane;
-            const unsigned u = __float_as_uint(s < S ? s_tm[s] : -INFINITY);
-            kv[i] = u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+            kv[i] = orderable(s < S ? s_tm[s] : -INFINITY);
             best = max(best, kv[i]);
         }
         const unsigned ninf = 0x007FFFFFu;                  // orderable key of -inf
@@ -627,7 +580,7 @@ __global__ __launch_bounds__(LE_NT, 4) void logits_eval_rows(const void *__restr
                 if (cntc >= k) x = c;
             }
         }
-        if (lane == 0) s_t = __uint_as_float(x ^ ((x >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+        if (lane == 0) s_t = unorderable(x);
     } else if (wave > 0 || !want_k || s_nonempty < k) {
         // level bests: the slices of level l are the contiguous range [level_first[l], level_first[l + 1]); waves 1 .. 7 (all eight when
         // no threshold is wanted) reduce the levels from the staged keys while wave 0 finds the threshold
@@ -635,12 +588,7 @@ __global__ __launch_bounds__(LE_NT, 4) void logits_eval_rows(const void *__restr
         for (int l = wave - w0; l < n_levels; l += nw) {
             unsigned long long m = 0ull;
             for (int s = level_first[l] + lane; s < level_first[l + 1]; s += 64) { const unsigned long long x = s_keys[s]; m = x > m ? x : m; }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const unsigned hi = __shfl_xor((unsigned)(m >> 32), o), lo = __shfl_xor((unsigned)m, o);
-                const unsigned long long x = ((unsigned long long)hi << 32) | lo;
-                m = x > m ? x : m;
-            }
+            m = wave_max_u64(m);
             if (lane == 0) s_lkey[l] = m;
         }
     }
@@ -649,18 +597,8 @@ __global__ __launch_bounds__(LE_NT, 4) void logits_eval_rows(const void *__restr
         const int l = lane;
         Best b = {-INFINITY, 0x7fffffff};
         if (l < n_levels) {
-            const unsigned long long m = l < 32 ? s_lkey[l] : 0ull;
-            if (m) {
-                const unsigned u = (unsigned)(m >> 32);
-                b.v = __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-                b.p = 0x7fffffff - (int)(unsigned)m;
-            }
-            const int fo = filler_pos[l];
-            const bool has_c = b.p < n_train, has_f = fo >= 0;
-            int win;
-            if (has_c && (!has_f || b.v > -1.0f || (b.v == -1.0f && b.p < fo))) win = b.p;
-            else win = has_f ? fo : b.p;
-            out_level[(int64_t)row * n_levels + l] = train_cols[win];
+            b = best_of_key(l < 32 ? s_lkey[l] : 0ull);
+            out_level[(int64_t)row * n_levels + l] = train_cols[level_winner(b, filler_pos[l], n_train)];
         }
         const Best top = wave_best(b);
         if (lane == 0 && out_top1) out_top1[row] = top.p < n_train ? train_cols[top.p] : -1;
@@ -734,12 +672,7 @@ __global__ __launch_bounds__(LE_NT, 4) void logits_eval_rows(const void *__restr
     if (HGR_LAB_ON(dbg == 4)) return;
     const int cnt = s_cnt;
     if (cnt <= LE_CAP) {
-        for (int c = tid; c < cnt; c += LE_NT) {
-            const float v = s_cv[c]; const int p = s_cp[c];
-            int rk = 0;
-            for (int j = 0; j < cnt; ++j) rk += better(s_cv[j], s_cp[j], v, p) ? 1 : 0;
-            if (rk < k) out_topk[(int64_t)row * k + rk] = test_cols[p];
-        }
+        rank_and_emit<LE_NT>(s_cv, s_cp, cnt, k, tid, [&](int rk, float, int p) { out_topk[(int64_t)row * k + rk] = test_cols[p]; });
         return;
     }
     // heavily duplicated data (more than LE_CAP elements tie at the threshold): every group that reaches t becomes a recompute
@@ -756,14 +689,8 @@ __global__ __launch_bounds__(LE_NT, 4) void logits_eval_rows(const void *__restr
     for (int j = 0; j < k; ++j) {
         Best b = {-INFINITY, 0x7fffffff};
         scan([&](float v, int te) { if (better(last.v, last.p, v, te) && better(v, te, b.v, b.p)) { b.v = v; b.p = te; } });
-        b = wave_best(b);
-        __syncthreads();
-        if (lane == 0) { s_bv[wave] = b.v; s_bp[wave] = b.p; }
-        __syncthreads();
-        Best w = {s_bv[0], s_bp[0]};
-        for (int i = 1; i < LE_NW; ++i) if (better(s_bv[i], s_bp[i], w.v, w.p)) { w.v = s_bv[i]; w.p = s_bp[i]; }
-        if (tid == 0) out_topk[(int64_t)row * k + j] = w.p < n_test ? test_cols[w.p] : -1;
-        last = w;
+        last = block_best<LE_NW>(b, s_bv, s_bp, tid);
+        if (tid == 0) out_topk[(int64_t)row * k + j] = last.p < n_test ? test_cols[last.p] : -1;
     }
 }
 
@@ -782,9 +709,6 @@ int hgr_logits_eval_rows_launch(const void *feat, const void *zslp, int D, int S
     HGR_CHECK_LAUNCH("hgr_logits_eval (row stage)");
     return HGR_OK;
 }
-
-namespace {
-}  // namespace
 
 extern "C" int hgr_topk_rows(const float *logits, int64_t ld, const int32_t *cols, int n_cols, int k,
                              int32_t *out_idx, float *out_val, int rows, void *stream) {
@@ -899,12 +823,9 @@ extern "C" int hgr_eval_rows(const float *logits, int64_t ld, int n_nodes, const
     HGR_REQUIRE(logits && lvl8 && train_pos && train_cols && filler_pos && out_level, "hgr_eval_rows: null operand");
     HGR_REQUIRE(rows >= 1 && n_nodes >= 1 && ld >= n_nodes && n_train >= 1 && n_levels >= 1 && n_levels <= 32, "hgr_eval_rows: bad sizes (n_levels <= 32)");
     HGR_REQUIRE(k == 0 || (out_topk && test_pos && test_cols && k >= 1 && k <= 32 && n_test >= k), "hgr_eval_rows: bad top-k arguments");
-    static const bool regs = getenv("HGR_EVAL_REGS") != nullptr;      // diagnostics: the register-accumulator variant
-    if (n_levels <= 16 && !regs) hipLaunchKernelGGL(eval_rows_lds, dim3(rows), dim3(EL_NT), 0, (hipStream_t)stream, logits, ld, n_nodes, lvl8, train_pos, train_cols,
-                                                    n_train, n_levels, filler_pos, test_pos, test_cols, n_test, k, out_level, out_top1, out_topk);
-    else if (n_levels <= 16) hipLaunchKernelGGL((eval_rows<16>), dim3(rows), dim3(EV_NT), 0, (hipStream_t)stream, logits, ld, n_nodes, lvl8, train_pos, train_cols, n_train,
-                                           n_levels, filler_pos, test_pos, test_cols, n_test, k, out_level, out_top1, out_topk);
-    else hipLaunchKernelGGL((eval_rows<32>), dim3(rows), dim3(EV_NT), 0, (hipStream_t)stream, logits, ld, n_nodes, lvl8, train_pos, train_cols, n_train,
+    if (n_levels <= EL_NLV) hipLaunchKernelGGL(eval_rows_lds, dim3(rows), dim3(EL_NT), 0, (hipStream_t)stream, logits, ld, n_nodes, lvl8, train_pos, train_cols,
+                                               n_train, n_levels, filler_pos, test_pos, test_cols, n_test, k, out_level, out_top1, out_topk);
+    else hipLaunchKernelGGL(eval_rows, dim3(rows), dim3(EV_NT), 0, (hipStream_t)stream, logits, ld, n_nodes, lvl8, train_pos, train_cols, n_train,
                             n_levels, filler_pos, test_pos, test_cols, n_test, k, out_level, out_top1, out_topk);
     HGR_CHECK_LAUNCH("hgr_eval_rows");
     return HGR_OK;

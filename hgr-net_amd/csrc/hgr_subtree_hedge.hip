@@ -21,16 +21,6 @@ constexpr float SH_INV = 9.313225746154785e-10f;   // 2^-30
 // function, so both see the same bits
 __device__ __forceinline__ float hedge_exp(float x, float m, float tau) { return expf(tau * (x - m)); }
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
-        const unsigned long long w = ((unsigned long long)hi << 32) | lo;
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(SH_NT) void subtree_hedge(const float *__restrict__ x, int64_t ld, int n_nodes, const int32_t *__restrict__ cand_pos,
                                                        const int32_t *__restrict__ anc_ptr, const int32_t *__restrict__ anc_nodes, float tau,
                                                        const uint32_t *__restrict__ thr, int T, int32_t *__restrict__ pick,

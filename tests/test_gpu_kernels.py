@@ -265,10 +265,11 @@ def test_topk_rows_exact(n, k):
 
 
 def test_topk_rows_duplicates_and_fallback():
-    """heavily duplicated values: exact tie order, and the candidate-overflow fallback path"""
+    """heavily duplicated values: exact tie order.  Candidates are ordered by (value, position), so equal values do not tie: these rows
+    give about 20 candidates and stay on the ranked path (the overflow fallback: test_select_fallback_rounds)"""
     rows, n, k = 3, 5000, 20
     lg = torch.zeros(rows, n)
-    lg[0] = 0.25                                             # all equal -> every element is a candidate (fallback)
+    lg[0] = 0.25                                             # all equal: the order is the position order alone
     lg[1] = torch.from_numpy((synth.randint(1, "dup", n, 0, 7)).astype(np.float32))   # 7 distinct values
     lg[2, ::2] = 1.0                                         # 2500 ties for the maximum
     idx, val = ops.topk_rows(lg.to(DEV), k, n_cols=n, want_values=True)
@@ -481,12 +482,14 @@ def test_gemm_race_screen_deep_pipeline():
                 assert torch.equal(out, first), (m, n, k, it)
 
 
-@pytest.mark.parametrize("n,levels,dup", [(90, 8, False), (48, 5, False), (3000, 12, False), (21841, 12, False), (5000, 6, True)])
+@pytest.mark.parametrize("n,levels,dup", [(90, 8, False), (48, 5, False), (3000, 12, False), (21841, 12, False), (5000, 6, True),
+                                          (500, 20, False), (48, 20, False)])
 def test_eval_rows_fused_exact(n, levels, dup):
-    """hgr_eval_rows (LDS-atomic level-segmented arg-max + top-1 + top-k) == the oracle's per-level masking / top-k, bit-exact."""
+    """hgr_eval_rows (level-segmented arg-max + top-1 + top-k) == the oracle's per-level masking / top-k, bit-exact.  Up to 16 levels:
+    the LDS-accumulator kernel, more: the register-accumulator kernel; n == 48: fewer than k non-empty slices (every test element a candidate)."""
     rows, k = 4, 20
     lg = _rand((rows, n), 70 + n, 0.05)
-    if dup:                                                  # heavy duplication: exercises tie order and the in-kernel fallback
+    if dup:                                                  # heavy duplication: tie order (about 20 candidates: the ranked path, not the fallback)
         lg = torch.from_numpy(synth.randint(5, "dupv", rows * n, 0, 3).astype(np.float32).reshape(rows, n)) * 0.1
     lg[0, 3] = lg[0, 17]
     depth = synth.randint(2, "depth", n, 0, levels).astype(np.int32)
@@ -510,6 +513,74 @@ def test_eval_rows_fused_exact(n, levels, dup):
     for r in range(rows):
         assert int(top1[r, 0]) == tr[tree_ref.topk_desc(lg[r, torch.from_numpy(tr)].numpy(), 1)[0]]
         assert np.array_equal(topk[r].cpu().numpy(), test[tree_ref.topk_desc(lg[r, torch.from_numpy(test.astype(np.int64))].numpy(), k)])
+
+
+def _n_candidates(v, pos, slc, k, escape):
+    """Host restatement of the top-k kernels' candidate count for one row: elements (value v, subset position pos) fall into 256 slices
+    (slc), the threshold is the k-th best slice maximum in (value, position) order and every element not worse than it is a candidate,
+    i.e. the threshold's global rank + 1.  `escape`: fewer than k non-empty slices make every element a candidate (the eval_rows kernels)."""
+    order = np.lexsort((pos, -v.astype(np.float64)))          # best first: larger value, then lower position
+    rank = np.empty(len(v), dtype=np.int64)
+    rank[order] = np.arange(len(v))
+    best = np.full(256, len(v), dtype=np.int64)
+    np.minimum.at(best, slc, rank)
+    nonempty = int((best < len(v)).sum())
+    if escape and nonempty < k:
+        return len(v)
+    return int(np.sort(best)[min(k, nonempty) - 1]) + 1
+
+
+def test_select_fallback_rounds():
+    """The candidate-overflow fallback (k rounds of block arg-max) of topk_rows and of both hgr_eval_rows kernels: "large" values on
+    columns that fill only 18 of a kernel's 256 slices, so the k-th best slice maximum is a "small" one and all ~1 150 large elements
+    are candidates of a list that holds 1 024.  Row 0: three distinct large values (value order and position ties), row 1: all large
+    values equal, row 2: plain random (the ranked path in the same launch).  The candidate counts are asserted on the host first."""
+    rows, n, k, cap = 3, 16384, 20, 1024
+    base = _rand((rows, n), 90, 0.05)
+    c = np.arange(n)
+    perm = np.argsort(synth.uniform(6, "perm", n), kind="stable").astype(np.int32)
+    tiers = torch.from_numpy((1.0 + 0.5 * (c % 3)).astype(np.float32))
+
+    def plant(big):
+        lg = base.clone()
+        big = torch.from_numpy(big)
+        lg[0, big] = tiers[big]
+        lg[1, big] = 1.0
+        return lg
+
+    # hgr_eval_rows: every column is a test column (unsorted positions); a column's slice is fixed by the column
+    lg = plant(c % 512 < 36)
+    test = perm
+    te_of_col = np.empty(n, dtype=np.int64)
+    te_of_col[test] = c
+    train = perm[: n - n // 3].copy()
+    tr = train.astype(np.int64)
+    for levels, slc in ((6, (c % 512) >> 1), (20, (c % 1024) >> 2)):       # LDS-accumulator kernel, register-accumulator kernel
+        counts = [_n_candidates(lg[r].numpy(), te_of_col, slc, k, True) for r in range(rows)]
+        assert counts[0] > cap and counts[1] > cap and counts[2] <= cap, (levels, counts)
+        depth = synth.randint(2, "depth", n, 0, levels).astype(np.int32)
+        index = ops.EvalIndex(torch.from_numpy(depth).to(DEV), torch.from_numpy(train).to(DEV), torch.from_numpy(test).to(DEV), levels)
+        lvl, top1, topk = ops.eval_rows(lg.to(DEV), index, k)
+        for l in range(levels):
+            same = [int(i) for i in np.nonzero(depth == l)[0]]
+            assert np.array_equal(lvl[:, l].cpu().numpy(), tree_ref.level_argmax(lg.numpy(), tr, same, n)), (levels, l)
+        for r in range(rows):
+            assert int(top1[r, 0]) == tr[tree_ref.topk_desc(lg[r, torch.from_numpy(tr)].numpy(), 1)[0]]
+            want = test[tree_ref.topk_desc(lg[r, torch.from_numpy(test.astype(np.int64))].numpy(), k)]
+            assert np.array_equal(topk[r].cpu().numpy(), want), (levels, r)
+
+    # hgr_topk_rows: the slice is fixed by the subset position
+    cols = perm
+    big = np.zeros(n, dtype=bool)
+    big[cols[c % 256 < 18]] = True
+    lg = plant(big)
+    counts = [_n_candidates(lg[r, torch.from_numpy(cols.astype(np.int64))].numpy(), c, c % 256, k, False) for r in range(rows)]
+    assert counts[0] > cap and counts[1] > cap and counts[2] <= cap, counts
+    idx, val = ops.topk_rows(lg.to(DEV), k, cols=torch.from_numpy(cols).to(DEV), want_values=True)
+    for r in range(rows):
+        want = cols[tree_ref.topk_desc(lg[r, torch.from_numpy(cols.astype(np.int64))].numpy(), k)]
+        assert np.array_equal(idx[r].cpu().numpy(), want), r
+        assert np.array_equal(val[r].cpu().numpy(), lg[r, torch.from_numpy(want.astype(np.int64))].numpy()), r
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -811,13 +882,16 @@ def test_vit_embed_ln_stats_equals_unfused(dt):
 
 # ---- logits GEMM with the evaluation in its epilogue (hgr_logits_eval) --------------------------------------------------------
 @pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("case", ["n21841", "ragged_rows", "empty_level", "ties", "all_equal", "clustered_test", "d1024"])
+@pytest.mark.parametrize("case", ["n21841", "ragged_rows", "empty_level", "ties", "all_equal", "all_equal_wide", "clustered_test", "d1024"])
 def test_logits_eval_bit_exact_vs_gemm_plus_eval_rows(dt, case):
     """hgr_logits_eval (no logits in memory: tile stage -> per-slice keys / maxima, row stage -> level arg-max, top-1, recomputed
     candidates -> top-20) must give EXACTLY the ids of hgr_gemm_nt (fp32 logits) + hgr_eval_rows on the same operands
     (main.py:136-176 on model/clip_tree.py:331): the full-size class matrix, ragged row counts, an empty level, exact ties
-    (duplicated class rows), all-equal logits (the k-round fallback), a tiny clustered test set, D = 1024."""
+    (duplicated class rows), all-equal logits (1 500 test elements reach the threshold: still the ranked path; `all_equal_wide`: 2 500,
+    more than the candidate list holds - the k-round fallback), a tiny clustered test set, D = 1024."""
     rows, n, d, levels, k = 64, 3000, 256, 9, 20
+    if case == "all_equal_wide":
+        rows, n = 8, 5000
     if case == "n21841":
         rows, n, d, levels = 512, 21841, 512, 12
     if case == "ragged_rows":
@@ -831,7 +905,7 @@ def test_logits_eval_bit_exact_vs_gemm_plus_eval_rows(dt, case):
     if case == "ties":
         z[5::7] = z[3]                                        # many identical class rows: exact ties across levels and subsets
         z[100:140] = z[99]
-    if case == "all_equal":
+    if case in ("all_equal", "all_equal_wide"):
         z[:] = z[0]
     depth = synth.randint(3, "depth", n, 0, levels).astype(np.int32)
     depth[:3] = 0
@@ -842,6 +916,8 @@ def test_logits_eval_bit_exact_vs_gemm_plus_eval_rows(dt, case):
     test = perm[n - n // 2:].copy()                           # unsorted: tie order follows the subset positions
     if case == "clustered_test":
         test = np.arange(40, 64, dtype=np.int32)[::-1].copy()
+    if case == "all_equal_wide":
+        assert len(test) > 2048                               # LE_CAP: every test element reaches the threshold, the list overflows
     f16, z16 = f.to(dt).to(DEV), z.to(dt).to(DEV)
     index = ops.EvalIndex(torch.from_numpy(depth).to(DEV), torch.from_numpy(train).to(DEV), torch.from_numpy(test).to(DEV), levels)
     ld = (n + 63) // 64 * 64

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Dev tool: time the evaluation kernels on a random [512, 21841] logits matrix."""
+"""Dev tool: time the evaluation kernels on a random [512, 21841] logits matrix.  Optional argument: the number of levels (default 12;
+more than 16 takes hgr_eval_rows to its register-accumulator kernel)."""
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -13,7 +14,7 @@ def timeit(fn, iters=20):
     for _ in range(iters): fn()
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / iters * 1e3
-B, N, L = 512, 21841, 12
+B, N, L = 512, 21841, int(sys.argv[1]) if len(sys.argv) > 1 else 12
 ld = (N + 63) // 64 * 64
 lg = (torch.randn(B, ld, device="cuda") * 0.05)[:, :N]
 depth = torch.randint(0, L, (N,), dtype=torch.int32, device="cuda")

@@ -11,6 +11,8 @@ for r in $(seq 1 "$rounds"); do
     tag=$(basename "$lib" .so)
     if [ "$lib" = "tree" ]; then env -u HGR_LIB "$@" > "$out/${tag}_r${r}.log" 2>&1
     else HGR_LIB="$PWD/$lib" "$@" > "$out/${tag}_r${r}.log" 2>&1; fi
+    rc=$?
     echo "$tag round $r: $(tail -1 "$out/${tag}_r${r}.log" | cut -c1-1500)"
+    if [ $rc -ne 0 ]; then echo "$tag round $r: exit status $rc, stopping"; exit $rc; fi    # nothing more is started after a failed process
   done
 done
