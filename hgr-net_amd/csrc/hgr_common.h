@@ -210,6 +210,15 @@ __device__ __forceinline__ float unorderable(unsigned u) { return __uint_as_floa
 __device__ __forceinline__ unsigned long long key_of(float v, int p) { return ((unsigned long long)orderable(v) << 32) | (unsigned)(0x7fffffff - p); }
 __device__ __forceinline__ void key_decode(unsigned long long m, float &v, int &p) { v = unorderable((unsigned)(m >> 32)); p = 0x7fffffff - (int)(unsigned)m; }
 
+// ---- a target's path against the level arg-maxes (main.py:162-191), shared by hgr_eval_report_rows and hgr_set_counters_rows -----------
+// level_pick(): the arg-max of the level `le` of one path node, from the row's lv[n_levels]; -2 (never a node id) for a level outside
+// the table.  path_edges(): with bit i of mm = "path position i is matched by its level's pick", the consecutive matched pairs of a path
+// of L nodes - the single match when L == 1 (main.py:179-180).  point = __popc(mm).
+__device__ __forceinline__ int level_pick(const int32_t *__restrict__ lv_row, int n_levels, int le) {
+    return (unsigned)le < (unsigned)n_levels ? lv_row[le] : -2;
+}
+__device__ __forceinline__ unsigned path_edges(unsigned mm, int L) { return L == 1 ? (mm & 1u) : (unsigned)__popc(mm & (mm >> 1)); }
+
 // sum over the 16 lanes of a DPP row (lanes with equal lane >> 4), result in every lane of the row; fixed order.
 // Must be executed by all lanes of the wave's rows it concerns (no divergence inside a row).
 __device__ __forceinline__ float row16_sum(float v) {

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(ERR_NT) void eval_report_rows(const int32_t *__rest
             Lx = anc_ptr[x + 1] - ox;
             if (Lx < 1 || Lx > ERR_MAXL) Lx = 0;
         }
-        const int q = (unsigned)le < (unsigned)n_levels ? lv[r * n_levels + le] : -2;      // -2: never a node id, never pa
+        const int q = level_pick(lv + r * n_levels, n_levels, le);            // -2: never a node id, never pa
         const bool qin = (unsigned)q < (unsigned)n_nodes;
         int par = -2;                                                         // parent of the pick; -1 = "root", -2 = no valid pick
         if (half == 0 && live && qin) {
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(ERR_NT) void eval_report_rows(const int32_t *__rest
         const unsigned hh = (unsigned)__ballot(live && pa == t1);             // low half: path positions that are the row's top-1
         const unsigned mm = (unsigned)__ballot(live && q == pa);              // path positions matched by their level's arg-max
         const unsigned point = __popc(mm);
-        const unsigned edge = L == 1 ? (mm & 1u) : __popc(mm & (mm >> 1));    // consecutive matched pairs; L == 1: main.py:179-180
+        const unsigned edge = path_edges(mm, L);                              // consecutive matched pairs; L == 1: main.py:179-180
         // chain: every pick is a node, the first one hangs under the root, every next one under the pick before it
         const int qprev = __shfl_up(q, 1);
         const bool link = qin && par == (pos == 0 ? -1 : qprev);

@@ -50,18 +50,24 @@ def path_weight_table(model, method: str) -> torch.Tensor:
 
 class Evaluator:
     def __init__(self, model, report: bool = False, decode: str = "flat", decode_weights: str = "increasing", hedge=None,
-                 hedge_temperature: Optional[float] = None):
+                 hedge_temperature: Optional[float] = None, sets=None):
         """``decode``: what the predictions are taken from - "flat": the logits (the reference); "path": the path scores of
         hgr_path_scores, every node scored by the ``decode_weights``-weighted logits along its root-to-node path.  Everything behind
         hgr_eval_rows (counters, report, packed batches, all-reduces) is the same for both.
         ``hedge``: 1..8 thresholds in (0, 1], strictly increasing - hedged predictions (hgr_subtree_hedge on what hgr_eval_rows gets,
         candidates = the test classes; hgr_hedge_counters_rows behind the counters), read with hedge_table() / hedge_dict().
-        ``hedge_temperature``: the softmax's, default the model's ``logit_scale.exp()``, read once here."""
+        ``hedge_temperature``: the softmax's, default the model's ``logit_scale.exp()``, read once here.
+        ``sets``: an ordered mapping name -> node ids, 1..16 candidate sets scored in the same run (hgr_set_ranks on what
+        hgr_eval_rows gets, hgr_set_counters_rows behind the counters), read with sets_table() / sets_dict().  A row counts in a set
+        when its class is a member; its hits are the rank of its class among the set's columns, its hit / path / point ratios come
+        from the train columns like the main counters' - per set, what a model built with that set as candidates_test counts."""
         if decode not in DECODES:
             raise ValueError(f"decode {decode!r}: one of {DECODES}")
         thr = None if hedge is None else ops.hedge_thresholds(hedge)          # ValueError before anything is allocated
         if hedge is not None and hedge_temperature is not None and not (0.0 < float(hedge_temperature) < float("inf")):
             raise ValueError(f"hedge_temperature {hedge_temperature!r}: finite, > 0")
+        if sets is not None:
+            sets = ops.check_sets(sets, len(model.nodes))                      # ValueError before anything is allocated
         self.model = model
         self.decode = decode
         # path decoding: the weight table, made once, and one scores buffer, grown to the largest batch seen; flat: nothing extra
@@ -81,6 +87,12 @@ class Evaluator:
             self.hedge_tab = torch.zeros((len(thr), ops.HEDGE_COLS), dtype=torch.int64, device=dev)
         self.n_levels = model.max_depth + 1
         self.index = ops.EvalIndex(model.depth32, model.train_index32, model.test_index32, self.n_levels)   # dense per-column maps, built once
+        # candidate sets: the per-column maps, the int64 table [S, 33, SETS_COLS] and the rank / top-1 buffers of the current batch (grown
+        # to the largest batch seen) - or None = nothing is allocated, nothing extra is launched
+        self.sets = self.sets_tab = self._sets_buf = None
+        if sets is not None:
+            self.sets = ops.SetIndex(self.index, sets)
+            self.sets_tab = torch.zeros((self.sets.n_sets, ops.REPORT_MAXL + 1, ops.SETS_COLS), dtype=torch.int64, device=dev)
         self._anc = None         # ancestor paths of every node as a device CSR (see _ancestor_tables)
         self._plan = None        # level-sorted class matrix of the fused logits + evaluation kernel, built on first use
 
@@ -139,16 +151,19 @@ class Evaluator:
         parents, levels64, levels32, _ = self._parents(target)
         tg = None if targets is None else self._row_targets(targets)
         rt = csr = None
-        if self.report is not None or self.hedge is not None:    # both score rows: without targets, ``target`` for every row
+        if self.report is not None or self.hedge is not None or self.sets is not None:    # all three score rows: without targets, ``target`` for every row
             rt = tg if tg is not None else torch.full((like.shape[0],), int(target), dtype=torch.int64, device=like.device)
             csr = self._ancestor_csr()
 
-        def score(lv, p1, pred, pick=None):
+        def score(lv, p1, pred, pick=None, set_rank=None):
             ops.eval_counters(pred, tg, int(target), p1.view(-1), lv, parents, levels32, self.acc)
             if self.report is not None:
                 ops.eval_report_rows(pred, rt, p1.view(-1), lv, *csr, self.report)
             if pick is not None:
                 ops.hedge_counters_rows(pick, rt, csr[0], csr[1], self.hedge_tab)
+            if set_rank is not None:
+                ops.set_counters_rows(set_rank, self._sets_top1(p1), rt, lv, *csr, self.sets_tab)
+        score.row_targets = rt
         return score, [t for t in (tg, rt) if t is not None], lambda lv: lv[:, levels64]        # dict_path [B, L]
 
     def _rows_scorer(self, targets: torch.Tensor):
@@ -156,12 +171,15 @@ class Evaluator:
         tg = self._row_targets(targets)
         csr = self._ancestor_csr()
 
-        def score(lv, p1, pred, pick=None):
+        def score(lv, p1, pred, pick=None, set_rank=None):
             ops.eval_counters_rows(pred, tg, p1.view(-1), lv, *csr, self.acc)
             if self.report is not None:
                 ops.eval_report_rows(pred, tg, p1.view(-1), lv, *csr, self.report)
             if pick is not None:
                 ops.hedge_counters_rows(pick, tg, csr[0], csr[1], self.hedge_tab)
+            if set_rank is not None:
+                ops.set_counters_rows(set_rank, self._sets_top1(p1), tg, lv, *csr, self.sets_tab)
+        score.row_targets = tg
         return score, [tg], lambda lv: lv
 
     def _join_tail(self) -> None:
@@ -196,21 +214,42 @@ class Evaluator:
         pick, pmass = (b[:rows * t].view(rows, t) for b in self._hedge_pick)
         return ops.subtree_hedge(scores, self.index.test_pos, ptr, nodes, self.hedge_temperature, self._hedge_thr, pick, pmass, mass_out)
 
+    def set_ranks(self, scores: torch.Tensor, targets: Optional[torch.Tensor] = None):
+        """hgr_set_ranks of ``scores`` [B, >= N] (what hgr_eval_rows gets) for this Evaluator's candidate sets, into its buffers:
+        (rank int32 [B, S] or None without targets, top1 int32 [B, S]), valid until the next batch."""
+        assert self.sets is not None, "Evaluator(model, sets={...}) keeps the candidate sets"
+        rows, s = scores.shape[0], self.sets.n_sets
+        if self._sets_buf is None or self._sets_buf.numel() < 3 * rows * s or self._sets_buf.device != scores.device:
+            self._sets_buf = torch.empty(3 * rows * s, dtype=torch.int32, device=scores.device)
+        rank, top1 = (self._sets_buf[i * rows * s:(i + 1) * rows * s].view(rows, s) for i in range(2))
+        return ops.set_ranks(scores, self.sets, targets, rank if targets is not None else None, top1)
+
+    def _sets_top1(self, p1: torch.Tensor) -> torch.Tensor:
+        """The prediction whose ancestor hits every set counts: the top-1 over the TRAIN columns (main.py:157-160), the same for every
+        set like the level arg-maxes - hgr_set_counters_rows takes one prediction per row and set, so it is repeated per set."""
+        rows, s = p1.numel(), self.sets.n_sets
+        out = self._sets_buf[2 * rows * s:3 * rows * s].view(rows, s)          # behind this batch's rank and top-1 (set_ranks sized it)
+        out.copy_(p1.view(-1, 1).expand(rows, s))
+        return out
+
     def _add_logits(self, logits: torch.Tensor, scorer, want_outputs: bool):
         score, _, view = scorer
         self._join_tail()
         if self.decode == "path":                      # path decoding IS hgr_eval_rows on the path scores
             logits = self.path_scores(logits)
         lv, p1, pred = ops.eval_rows(logits, self.index, max(TOPK))
-        if self.hedge is None:
+        # the hedge and the candidate sets read the tensor hgr_eval_rows got: both compose with the two decodings
+        pick = None if self.hedge is None else self.hedge_picks(logits)[0]
+        set_rank = None if self.sets is None else self.set_ranks(logits, score.row_targets)[0]
+        if pick is None and set_rank is None:
             score(lv, p1, pred)
-        else:                                          # the hedge reads the tensor hgr_eval_rows got: the two decodings compose
-            score(lv, p1, pred, self.hedge_picks(logits)[0])
+        else:
+            score(lv, p1, pred, pick, set_rank)
         return (pred, view(lv)) if want_outputs else None
 
     def _add_images(self, imgs: torch.Tensor, scorer, want_outputs: bool):
         score, reads, view = scorer
-        if self.decode == "path" or self.hedge is not None:     # the fused kernel never has the whole row: logits -> (path scores, hedge) -> hgr_eval_rows
+        if self.decode == "path" or self.hedge is not None or self.sets is not None:     # the fused kernel never has the whole row: logits -> (path scores, hedge, sets) -> hgr_eval_rows
             return self._add_logits(self.model(imgs, None, static_output=True), scorer, want_outputs)
         plan = self._fused_plan()
         if not plan.supported:                        # a hierarchy beyond hgr_logits_eval's capacity: logits + hgr_eval_rows
@@ -247,8 +286,9 @@ class Evaluator:
 
     def fused_ok(self) -> bool:
         """hgr_logits_eval needs an embedding width that is a multiple of 128 (<= 1024) and <= 32 levels - and flat decoding: the path
-        scores of a column read other columns of its row, which the fused kernel never holds together; so does the softmax of a hedge."""
-        if self.decode == "path" or self.hedge is not None:
+        scores of a column read other columns of its row, which the fused kernel never holds together; so do the softmax of a hedge and the ranks of
+        the candidate sets."""
+        if self.decode == "path" or self.hedge is not None or self.sets is not None:
             return False
         d = self.model._zsl16.shape[1] if self.model._zsl16 is not None else 0
         if not (d % 128 == 0 and 128 <= d <= 1024 and self.n_levels <= 32 and self.index.n_test >= max(TOPK)):
@@ -291,13 +331,7 @@ class Evaluator:
         if tripped:                                        # activations left the guarded 16-bit range AFTER the first-pass check
             import warnings
             warnings.warn(f"hgr_net_amd: LayerNorm-folding range guard tripped during this evaluation {tripped}: rerun with HGR_LN_FUSED=0")
-        n = c["num_sample"]
-        s, _ = count_acc({k: c[f"hits@{k}"] for k in TOPK}, n)
-        out = "\n" + s
-        out += " hit_ratio(%):{:.2f}".format(c["hits_all"] / n * 100.0)
-        out += " path_ratio(%):{:.2f}".format(c["path_all"] / n * 100.0)
-        out += " point_ratio(%):{:.2f}".format(c["point_all"] / n * 100.0)
-        return out
+        return "\n" + metric_text(c)
 
     def report_table(self, group=None) -> torch.Tensor:
         """The hierarchy report's table as a CPU int64 tensor [ops.REPORT_LEN] (one D2H copy); with a process group the tables of
@@ -319,6 +353,16 @@ class Evaluator:
         assert self.hedge_tab is not None, "Evaluator(model, hedge=(...)) keeps the hedge table"
         return self._read_table(self.hedge_tab, group)
 
+    def sets_table(self, group=None) -> torch.Tensor:
+        """The candidate sets' table as a CPU int64 tensor [S, ops.REPORT_MAXL + 1, ops.SETS_COLS] (one D2H copy); with a process group
+        summed over the ranks first, through the int64 all-reduce of report_table."""
+        assert self.sets_tab is not None, "Evaluator(model, sets={...}) keeps the candidate sets' table"
+        return self._read_table(self.sets_tab, group)
+
+    def sets_dict(self, group=None) -> dict:
+        """The candidate sets' results as plain Python values (sets_from_table), ready for json.dump."""
+        return sets_from_table(self.sets_table(group), self.sets.names, self.sets.sizes)
+
     def hedge_dict(self, group=None) -> dict:
         """The hedge outcomes as plain Python values (hedge_from_table), ready for json.dump."""
         return hedge_from_table(self.hedge_table(group), self.hedge, temperature=self.hedge_temperature)
@@ -326,6 +370,16 @@ class Evaluator:
     def report_dict(self, group=None) -> dict:
         """The hierarchy report as plain Python values (report_from_table), ready for json.dump."""
         return report_from_table(self.report_table(group), k=max(TOPK))
+
+
+def metric_text(c: Dict[str, float]) -> str:
+    """The metric line of main.test (main.py:205-214, without its leading newline) from the nine counters."""
+    n = c["num_sample"]
+    s, _ = count_acc({k: c[f"hits@{k}"] for k in TOPK}, n)
+    s += " hit_ratio(%):{:.2f}".format(c["hits_all"] / n * 100.0)
+    s += " path_ratio(%):{:.2f}".format(c["path_all"] / n * 100.0)
+    s += " point_ratio(%):{:.2f}".format(c["point_all"] / n * 100.0)
+    return s
 
 
 def _mistakes(hist) -> dict:
@@ -434,6 +488,105 @@ def format_hedge(rep: dict) -> str:
     return "\n".join(lines)
 
 
+def sets_from_table(table: torch.Tensor, names, sizes) -> dict:
+    """The table of hgr_set_counters_rows (CPU int64 [S, ops.REPORT_MAXL + 1, ops.SETS_COLS], layout in include/hgr.h) as plain Python
+    values; a pure function of the table.  Per set: its name, ``classes`` (its size), the nine counters of Evaluator.counters() - the
+    hits are sums over the path lengths, path_all = sum of edge / (L - 1) (edge at L = 1) and point_all = sum of point / L, one division
+    per path length in hgr_eval_counters_rows' order - acc@k and the three ratios in percent (None for a set without rows), and
+    ``by_depth`` with report_from_table's formulas (depth = L - 1; depths without rows are left out)."""
+    names, sizes = [str(n) for n in names], [int(n) for n in sizes]
+    assert table.dtype == torch.int64 and tuple(table.shape) == (len(names), ops.REPORT_MAXL + 1, ops.SETS_COLS) and not table.is_cuda
+    assert len(sizes) == len(names)
+    out = []
+    for name, size, tab in zip(names, sizes, table.tolist()):
+        tot = {k: 0 for k in COUNTERS}
+        tot["path_all"] = tot["point_all"] = 0.0
+        by_depth = []
+        for L in range(1, ops.REPORT_MAXL + 1):
+            row = dict(zip(ops.SETS_COL_NAMES, tab[L]))
+            n = row["rows"]
+            tot["path_all"] += row["edge"] / max(L - 1, 1)
+            tot["point_all"] += row["point"] / L
+            if n == 0:
+                continue
+            tot["num_sample"] += n
+            tot["hits_all"] += row["anc_hit"]
+            e = {"depth": L - 1, "rows": n}
+            for kk in TOPK:
+                tot[f"hits@{kk}"] += row[f"hit@{kk}"]
+                e[f"hits@{kk}"] = row[f"hit@{kk}"]
+                e[f"acc@{kk}"] = row[f"hit@{kk}"] / n * 100.0
+            e["hit_ratio"] = row["anc_hit"] / n * 100.0
+            e["path_ratio"] = row["edge"] / max(L - 1, 1) / n * 100.0
+            e["point_ratio"] = row["point"] / L / n * 100.0
+            by_depth.append(e)
+        n = tot["num_sample"]
+        e = {"name": name, "classes": size}
+        e.update(tot)
+        for kk in TOPK:
+            e[f"acc@{kk}"] = tot[f"hits@{kk}"] / n * 100.0 if n else None
+        for ratio, counter in (("hit_ratio", "hits_all"), ("path_ratio", "path_all"), ("point_ratio", "point_all")):
+            e[ratio] = tot[counter] / n * 100.0 if n else None
+        e["by_depth"] = by_depth
+        out.append(e)
+    return {"sets": out}
+
+
+def format_sets(rep: dict) -> str:
+    """One line per candidate set: name, classes and images, then the text Evaluator.summary() makes from the set's counters."""
+    lines = []
+    for e in rep["sets"]:
+        head = "set {} ({} classes, {} images): ".format(e["name"], e["classes"], e["num_sample"])
+        lines.append(head + (metric_text(e) if e["num_sample"] else "no images"))
+    return "\n".join(lines)
+
+
+def parse_eval_sets(text):
+    """``--eval_sets hop2,hop3,hop3+train`` -> (("hop2", ("hop2",)), ("hop3", ("hop3",)), ("hop3+train", ("hop3", "train"))): the
+    names of the candidate sets in their order, each the union of one or more split keys joined by ``+``."""
+    if text is None:
+        return None
+    if not isinstance(text, str):
+        return tuple((str(n), tuple(k)) for n, k in text)
+    out = []
+    for name in (t.strip() for t in text.split(",")):
+        keys = tuple(k.strip() for k in name.split("+"))
+        if not name or not all(keys):
+            raise ValueError(f"--eval_sets {text!r}: comma-separated names, each one split key or several joined by '+'")
+        if name in (n for n, _ in out):
+            raise ValueError(f"--eval_sets {text!r}: {name!r} is listed twice")
+        out.append((name, keys))
+    if not 1 <= len(out) <= ops.SETS_MAXS:
+        raise ValueError(f"--eval_sets {text!r}: {len(out)} candidate sets (1..{ops.SETS_MAXS})")
+    return tuple(out)
+
+
+def resolve_eval_sets(spec, splits, nodes, extra=None) -> dict:
+    """The candidate sets of ``spec`` (parse_eval_sets) as an ordered mapping name -> node ids (positions in ``nodes``): every split
+    key is looked up in ``splits`` (--split_path) and in ``extra`` (--eval_sets_file, a second mapping name -> wnids); the ids of a
+    union keep the order of its keys, a wnid listed by several of them counts once.  ValueError, naming the offender: a key found in
+    neither mapping or in both, a wnid absent from the hierarchy."""
+    extra = extra or {}
+    both = sorted(set(splits) & set(extra))
+    if both:
+        raise ValueError(f"--eval_sets_file: key {both[0]!r} is also a key of the split file")
+    pos = {w: i for i, w in enumerate(nodes)}
+    out = {}
+    for name, keys in spec:
+        ids, seen = [], set()
+        for k in keys:
+            if k not in splits and k not in extra:
+                raise ValueError(f"--eval_sets: unknown split key {k!r} (known: {sorted(set(splits) | set(extra))})")
+            for w in (splits[k] if k in splits else extra[k]):
+                if w not in pos:
+                    raise ValueError(f"--eval_sets: {w!r} of split {k!r} is not a node of the hierarchy")
+                if pos[w] not in seen:
+                    seen.add(pos[w])
+                    ids.append(pos[w])
+        out[name] = ids
+    return out
+
+
 def parse_hedge(text):
     """``--hedge 0.25,0.5,0.9`` -> (0.25, 0.5, 0.9); the values are checked by ops.hedge_thresholds."""
     if text is None or isinstance(text, (tuple, list)):
@@ -449,7 +602,7 @@ def parse_hedge(text):
 @torch.no_grad()
 def predict(model, imgs: torch.Tensor, k: int = max(TOPK), decode: str = "flat", decode_weights: str = "increasing",
             want_scores: bool = False, evaluator: Optional[Evaluator] = None, hedge=None, hedge_temperature: Optional[float] = None,
-            want_mass: bool = False) -> Dict[str, torch.Tensor]:
+            want_mass: bool = False, sets=None, targets: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """Classify a batch of images (after ``model.update_classifier()``): {"topk": int32 [B, k] node ids among the test classes, best
     first, "top1": int32 [B] the best train class, "levels": int32 [B, n_levels] the best train class of every depth level (the
     reference's -1 filler competes, as in hgr_eval_rows)} - hgr_eval_rows on the logits (``decode="flat"``) or on their path scores (``"path"``, weights
@@ -457,9 +610,12 @@ def predict(model, imgs: torch.Tensor, k: int = max(TOPK), decode: str = "flat",
     Evaluator of this model to reuse (its index, weight table and scores buffer; its decode settings then hold) - without one, a
     new one is built per call.  ``hedge`` (thresholds, with ``hedge_temperature``; or an ``evaluator`` built with them) adds "hedge":
     int32 [B, T], per threshold the deepest node whose subtree holds that much of the row's probability among the test classes (-1: none
-    does), and "hedge_mass": fp32 [B, T], that node's mass; ``want_mass`` adds "mass": fp32 [B, N], every node's subtree mass."""
+    does), and "hedge_mass": fp32 [B, T], that node's mass; ``want_mass`` adds "mass": fp32 [B, N], every node's subtree mass.
+    ``sets`` (a mapping name -> node ids; or an ``evaluator`` built with it) adds "set_top1": int32 [B, S], the best member of every
+    candidate set (-1: an empty set), and with ``targets`` (one class id per row) "set_rank": int32 [B, S], the number of the set's
+    members that come before the row's class (-1: the class is no member)."""
     ev = evaluator if evaluator is not None else Evaluator(model, decode=decode, decode_weights=decode_weights, hedge=hedge,
-                                                           hedge_temperature=hedge_temperature)
+                                                           hedge_temperature=hedge_temperature, sets=sets)
     if want_mass and ev.hedge is None:
         raise ValueError("want_mass needs hedge thresholds")
     scores = model(imgs.to(model.train_index.device), None, static_output=True)
@@ -475,6 +631,12 @@ def predict(model, imgs: torch.Tensor, k: int = max(TOPK), decode: str = "flat",
         out["hedge"], out["hedge_mass"] = pick.clone(), pmass.clone()   # the pick buffers are reused by the next batch
         if want_mass:
             out["mass"] = mass.to(torch.float32) * (1.0 / ops.HEDGE_SCALE)
+    if ev.sets is not None:
+        tg = None if targets is None else Evaluator._row_targets(torch.as_tensor(targets).to(scores.device))
+        rank, top1 = ev.set_ranks(scores, tg)
+        out["set_top1"] = top1.clone()                                  # the buffers are reused by the next batch
+        if rank is not None:
+            out["set_rank"] = rank.clone()
     return out
 
 
@@ -510,6 +672,10 @@ def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, gr
     hedge, hedge_path = parse_hedge(getattr(opts, "hedge", None)), getattr(opts, "hedge_report", None)
     if hedge is not None:
         kw.update(hedge=hedge, hedge_temperature=getattr(opts, "hedge_temperature", None))
+    set_spec, sets_path = parse_eval_sets(getattr(opts, "eval_sets", None)), getattr(opts, "eval_sets_report", None)
+    if set_spec is not None:
+        extra = getattr(opts, "eval_sets_file", None)
+        kw.update(sets=resolve_eval_sets(set_spec, splits or {}, model.nodes, json.load(open(extra)) if extra else None))
     ev = Evaluator(model, **kw)
     fused = ev.fused_ok() and os.environ.get("HGR_EVAL_FUSED", "1") != "0"
     packed = bool(getattr(opts, "pack_batches", False))
@@ -553,6 +719,14 @@ def test(opts, model, device, splits=None, loader: Optional[Iterable] = None, gr
                 with open(hedge_path, "w") as f:
                     json.dump(rep, f, indent=1)
             print(format_hedge(rep), flush=True)
+    if set_spec is not None:                             # one line per candidate set behind the metric string
+        rep = ev.sets_dict(group)
+        import torch.distributed as dist
+        if group is None or dist.get_rank() == 0:
+            if sets_path:
+                with open(sets_path, "w") as f:
+                    json.dump(rep, f, indent=1)
+            print(format_sets(rep), flush=True)
     if log:
         with open(model.save_path + "arugements.log", "a") as f:
             f.writelines(out + "\n")

@@ -90,6 +90,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "node whose subtree holds that much of the row's softmax over the test classes; outcomes are printed per threshold")
     p.add_argument("--hedge_temperature", default=None, type=float, help="--hedge: the softmax's temperature (default: the model's logit scale)")
     p.add_argument("--hedge_report", default=None, type=str, metavar="PATH", help="--hedge: also write the outcomes per threshold as JSON to PATH")
+    p.add_argument("--eval_sets", default=None, type=str, metavar="A,B,C+train",
+                   help="evaluation: also score every image against these candidate sets in the same run (hgr_set_ranks) - comma-separated "
+                        "split keys, X+Y = the union of two keys; one metric line per set is printed behind the metric string")
+    p.add_argument("--eval_sets_file", default=None, type=str, metavar="PATH",
+                   help="--eval_sets: a second JSON of name -> wnid list, looked up together with --split_path (a key in both is an error)")
+    p.add_argument("--eval_sets_report", default=None, type=str, metavar="PATH", help="--eval_sets: also write the per-set report as JSON to PATH")
     p.add_argument("--ref_quirks", default=False, action="store_true",
                    help="reproduce the reference's missing zero_grad() (gradients accumulate across steps, SURVEY F11-i)")
     return p

@@ -677,6 +677,92 @@ def hedge_counters_rows(pick: torch.Tensor, targets: torch.Tensor, anc_ptr: torc
               _dev(table), pick.shape[0], _stream())
 
 
+# candidate sets: mirrors HGR_SETS_* of include/hgr.h (one set's table is [REPORT_MAXL + 1][SETS_COLS], by the target's path length)
+SETS_MAXS = 16
+SETS_COL_NAMES = ("rows", "hit@1", "hit@2", "hit@5", "hit@10", "hit@20", "anc_hit", "point", "edge")
+SETS_COLS = len(SETS_COL_NAMES)                                    # 9
+
+
+def check_sets(sets, n_nodes: int) -> dict:
+    """``sets`` as an ordered dict name -> list of node ids, or ValueError: no mapping, no set or more than SETS_MAXS, an id twice in
+    one set, an id outside [0, n_nodes).  Host only."""
+    try:
+        items = [(str(k), [int(c) for c in (v.tolist() if hasattr(v, "tolist") else v)]) for k, v in dict(sets).items()]
+    except (TypeError, ValueError):
+        raise ValueError(f"sets {sets!r}: a mapping from a name to node ids") from None
+    if not 1 <= len(items) <= SETS_MAXS:
+        raise ValueError(f"sets: {len(items)} candidate sets (1..{SETS_MAXS})")
+    for name, ids in items:
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"sets[{name!r}]: a node id appears twice")
+        bad = [c for c in ids if not 0 <= c < n_nodes]
+        if bad:
+            raise ValueError(f"sets[{name!r}]: node id {bad[0]} outside the hierarchy (0..{n_nodes - 1})")
+    return dict(items)
+
+
+class SetIndex:
+    """The per-column maps of hgr_set_ranks for up to SETS_MAXS candidate sets, built once on the host: ``member`` int32 [n_nodes]
+    (bit s = column c belongs to set s, in the order of ``sets``), ``tie_key`` int32 [n_nodes] (the model's test classes keep their
+    position in the test subset, every other node follows in node order from n_test upward: a set listed in the model's test order
+    breaks ties the way hgr_eval_rows does), ``names`` and ``sizes``.  ``sets``: an ordered mapping name -> node ids.  ValueError,
+    before anything is allocated on the device: no set or more than SETS_MAXS, an id twice in one set, an id outside the hierarchy."""
+
+    def __init__(self, eval_index: EvalIndex, sets):
+        import numpy as np
+        n = eval_index.n_nodes
+        items = list(check_sets(sets, n).items())
+        member = np.zeros(n, dtype=np.int32)
+        for s, (name, ids) in enumerate(items):
+            member[np.asarray(ids, dtype=np.int64)] |= np.int32(1 << s)
+        key = np.full(n, -1, dtype=np.int64)
+        if eval_index.test_pos is not None:
+            key = eval_index.test_pos.cpu().numpy().astype(np.int64)
+        rest = key < 0
+        key[rest] = eval_index.n_test + np.arange(int(rest.sum()), dtype=np.int64)
+        dev = eval_index.lvl8.device
+        self.n_nodes, self.n_sets = n, len(items)
+        self.names = tuple(name for name, _ in items)
+        self.sizes = tuple(len(ids) for _, ids in items)
+        self.member = torch.from_numpy(member).to(dev)
+        self.tie_key = torch.from_numpy(key.astype(np.int32)).to(dev)
+
+
+def set_ranks(scores: torch.Tensor, index: SetIndex, targets: Optional[torch.Tensor] = None, rank: Optional[torch.Tensor] = None,
+              top1: Optional[torch.Tensor] = None):
+    """(rank int32 [rows, S] or None, top1 int32 [rows, S]) of hgr_set_ranks (definition in include/hgr.h): per candidate set of
+    ``index`` the number of its members that come before the row's target (-1: the target is no member, or no node) and its best
+    member (-1: an empty set).  ``scores``: what hgr_eval_rows gets, fp32 [rows, >= n_nodes], unit column stride - a view of a wider
+    buffer is fine; ``targets`` int64 [rows] or None (then only top1 is made)."""
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.stride(1) == 1
+    rows, s = scores.shape[0], index.n_sets
+    assert targets is None or (targets.dtype == torch.int64 and targets.is_contiguous() and targets.numel() == rows)
+    if top1 is None:
+        top1 = torch.empty((rows, s), dtype=torch.int32, device=scores.device)
+    if rank is None and targets is not None:
+        rank = torch.empty((rows, s), dtype=torch.int32, device=scores.device)
+    assert top1.dtype == torch.int32 and top1.shape == (rows, s) and top1.is_contiguous()
+    assert rank is None or (rank.dtype == torch.int32 and rank.shape == (rows, s) and rank.is_contiguous())
+    # the sizes go to the library as they are: it rejects what hgr.h lists, before anything is launched
+    _lib.call("hgr_set_ranks", _dev(scores), scores.stride(0), index.n_nodes, _dev(index.member), _dev(index.tie_key), s, _dev(targets),
+              _dev(rank if targets is not None else None), _dev(top1), rows, _stream())
+    return (rank if targets is not None else None), top1
+
+
+def set_counters_rows(rank: torch.Tensor, top1: torch.Tensor, targets: torch.Tensor, lv: torch.Tensor, anc_ptr: torch.Tensor,
+                      anc_nodes: torch.Tensor, anc_levels: torch.Tensor, table: torch.Tensor) -> None:
+    """Add one batch to the candidate sets' int64 table [S, REPORT_MAXL + 1, SETS_COLS] (hgr_set_counters_rows, include/hgr.h): a row
+    counts in set s when rank[r, s] >= 0 and it is no padding row of eval_counters_rows; exact integer counts only."""
+    assert rank.dtype == top1.dtype == lv.dtype == anc_ptr.dtype == anc_nodes.dtype == anc_levels.dtype == torch.int32
+    assert rank.dim() == 2 and rank.is_contiguous() and top1.shape == rank.shape and top1.is_contiguous() and lv.is_contiguous()
+    assert anc_ptr.is_contiguous() and anc_nodes.is_contiguous() and anc_levels.is_contiguous() and anc_ptr.numel() >= 2
+    assert table.dtype == torch.int64 and table.shape == (rank.shape[1], REPORT_MAXL + 1, SETS_COLS) and table.is_contiguous()
+    assert targets is not None and targets.dtype == torch.int64 and targets.is_contiguous() and targets.numel() == rank.shape[0]
+    assert lv.shape[0] == rank.shape[0]
+    _lib.call("hgr_set_counters_rows", _dev(rank), _dev(top1), rank.shape[1], _dev(targets), _dev(lv), lv.shape[1], _dev(anc_ptr), _dev(anc_nodes),
+              _dev(anc_levels), anc_ptr.numel() - 1, _dev(table), rank.shape[0], _stream())
+
+
 # ---- ModifiedResNet (RN) tower -------------------------------------------------------------------
 def conv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, b: int, h: int, wd: int, c: int,
                  stride: int = 1) -> torch.Tensor:

@@ -374,6 +374,41 @@ enum { HGR_HEDGE_COL_ROWS = 0, HGR_HEDGE_COL_ABSTAIN = 1, HGR_HEDGE_COL_EXACT = 
 int hgr_hedge_counters_rows(const int32_t *pick, int n_thr, const int64_t *targets, const int32_t *anc_ptr, const int32_t *anc_nodes,
                             int n_nodes, int64_t *table /* [n_thr][HGR_HEDGE_COLS] */, int rows, void *stream);
 
+/* Candidate sets: one pass over a scores row answers up to HGR_SETS_MAXS candidate sets at once - per set the rank of the row's own
+ * class among the set's columns and the set's best column.  scores fp32 [rows, ld], ld >= n_nodes: what hgr_eval_rows gets (the logits,
+ * or the path scores); member uint32 [n_nodes]: bit s of member[c] is set when column c belongs to set s (bits >= n_sets are ignored);
+ * tie_key int32 [n_nodes]: distinct over the members of every set, it only breaks ties; targets int64 [rows] or NULL.  Outputs: rank,
+ * top1 int32 [rows, n_sets].  For a row with scores x and columns c != d,
+ *   before(c, d) = x[c] > x[d], or x[c] == x[d] and tie_key[c] < tie_key[d]       (ordinary IEEE compares: -0 equals +0)
+ *   top1[r, s]   = the member of set s that no other member is before; -1 for an empty set
+ *   rank[r, s]   = the number of members c != t of set s with before(c, t), t = targets[r], when 0 <= t < n_nodes and t is a member
+ *                  of s; -1 otherwise
+ * With targets == NULL only top1 is written, and rank may be NULL.  A set listed in the order a subset was given to hgr_eval_rows, with
+ * tie_key = the position in it, has rank < k exactly where the target is inside that subset's top-k, and top1 = its first top-k column.
+ * Scores are finite (NaN: unspecified values, but no address is ever made from a score).  The outputs are exact integers: they depend
+ * on no lane, workgroup, row order or cut into launches.  No limit on n_nodes but int32 (no row is kept on the chip).  Rejected before
+ * anything is launched: a null required operand, rows < 1, n_nodes < 1, ld < n_nodes, n_sets outside 1..16, rank == NULL with targets.
+ * One workgroup per row on a capped grid that loops over rows, lanes stride the columns (16-byte loads of scores and member words when
+ * the row's base allows them); per lane and set a "beats the target" counter and the best member as a 64-bit key (order-preserving
+ * float bits of x + 0.0f, then the complement of the tie key); tie_key[c] is read only where a score compares equal or a lane's best
+ * changes. */
+#define HGR_SETS_MAXS 16
+int hgr_set_ranks(const float *scores, int64_t ld, int n_nodes, const uint32_t *member, const int32_t *tie_key, int n_sets,
+                  const int64_t *targets, int32_t *rank, int32_t *top1, int rows, void *stream);
+
+/* The counters of every candidate set: rank / top1 int32 [rows, n_sets] (what hgr_set_ranks wrote, or any other per-set prediction in
+ * top1's place), targets, lv and the ancestor CSR as for hgr_eval_report_rows, added into an int64 table
+ * [n_sets][HGR_REPORT_MAXL + 1][HGR_SETS_COLS] on the device.  Row r counts in set s exactly when rank[r, s] >= 0 and the row is not
+ * padding by hgr_eval_counters_rows' rule (target outside [0, n_nodes), or its path length L outside 1..32).  A counting row adds, in
+ * row L of set s: 1 to rows; 1 to hit@k for every k in (1, 2, 5, 10, 20) with rank[r, s] < k; to anc_hit the number of path nodes
+ * equal to top1[r, s]; point and edge as hgr_eval_report_rows defines them from lv (they are the same for every set).  64-bit integer
+ * adds only (per-launch counts in LDS, one flush per block): the table depends neither on the order of the rows nor on the cut into
+ * launches.  One wave per row, a fixed grid of at most 8 blocks; n_sets in 1..16, n_levels <= 32. */
+#define HGR_SETS_COLS 9   /* rows, hit@1, @2, @5, @10, @20, anc_hit, point, edge */
+int hgr_set_counters_rows(const int32_t *rank, const int32_t *top1, int n_sets, const int64_t *targets, const int32_t *lv, int n_levels,
+                          const int32_t *anc_ptr, const int32_t *anc_nodes, const int32_t *anc_levels, int n_nodes,
+                          int64_t *table /* [n_sets][HGR_REPORT_MAXL + 1][HGR_SETS_COLS] */, int rows, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * ModifiedResNet (RN50) tower, clip/model.py:93-150.  Activations are NHWC 16-bit ([B, H, W, C] =
  * a row-major [B*H*W, C] matrix), so every 1x1 convolution IS hgr_gemm_nt; inference BatchNorm
