@@ -76,6 +76,72 @@ def test_gemm_plans_match_golden(tmp_path, golden_dir):
     assert lib.hgr_gemm_plan_capture(None, 0) == 0
 
 
+def test_gemm_32bit_offset_guard_flips_at_4gb():
+    """gemm_nt_duo, gemm_nt_ws, gemm_nt_p8, the LayerNorm forms and hgr_gemm_nt_ln_mha address their operands with 32-bit byte offsets.
+    One step below M * lda * 2 = 2^32 (and N * ldw * 2 = 2^32) hgr_gemm_nt plans them, at the limit it falls back to the 128 / 256
+    kernels (64-bit pointers); the entry points that have no other kernel reject the call, and ops.ln_mha_ok / ops.gelu_dual_ok say
+    the same as the library on both sides.  With the plan capture armed nothing is launched and no operand is read, and a rejected
+    call launches nothing either: a small real tensor with a huge leading dimension is safe."""
+    from hgr_net_amd import _lib, ops
+    from hgr_net_amd._lib import EPI_BIAS, EPI_NONE, HGR_F16
+    lib = _lib.load()
+    p = torch.zeros(64, dtype=torch.float16).data_ptr()
+    assert p % 16 == 0
+    small, narrow = (1, 2), (3, 4, 5)                                  # HGR_KERNEL_128 / _256; _DUO / _WS / _P8
+
+    def nt(m, n, k, lda, ldw, epi=EPI_NONE, out32=1):
+        return [d["kernel"] for d in ops.gemm_plan(lambda: _lib.call("hgr_gemm_nt", p, lda, p, ldw, p, n, p, p, n, m, n, k, HGR_F16, epi, out32, 0))]
+
+    def limit(rows):                                                   # the smallest leading dimension with rows * ld * 2 >= 2^32, % 8 == 0
+        return -(-(1 << 32) // (2 * rows * 8)) * 8
+
+    prev_tile, prev_ws = ops.gemm_set_tile(0), lib.hgr_gemm_set_ws(0)
+    try:
+        for tile, ws, (m, n, k), epi, out32, kernel in ((0, 0, (8192, 4096, 128), EPI_NONE, 1, 3),       # gemm_nt_duo by shape
+                                                        (2, 0, (1024, 256, 128), EPI_NONE, 1, 3),        # ... and pinned
+                                                        (0, 1, (4096, 2048, 768), EPI_BIAS, 0, 4)):      # gemm_nt_ws
+            ops.gemm_set_tile(tile)
+            lib.hgr_gemm_set_ws(ws)
+            la, lw = limit(m), limit(n)
+            assert (m * (la - 8) * 2 < 1 << 32 <= m * la * 2) and (n * (lw - 8) * 2 < 1 << 32 <= n * lw * 2)
+            assert nt(m, n, k, la - 8, lw - 8, epi, out32) == [kernel]
+            for lda, ldw in ((la, k), (k, lw), (la, lw)):
+                plan = nt(m, n, k, lda, ldw, epi, out32)
+                assert plan and all(kn in small for kn in plan) and not any(kn in narrow for kn in plan), (tile, ws, lda, ldw, plan)
+    finally:
+        ops.gemm_set_tile(prev_tile)
+        lib.hgr_gemm_set_ws(prev_ws)
+
+    m, n, k = 1024, 256, 128
+    la, lw = limit(m), limit(n)
+    entries = {"hgr_gemm_nt_ln": lambda lda, ldw: (p, lda, p, ldw, p, n, p, p, p, 1e-5, m, n, k, HGR_F16, 0, 0),
+               "hgr_gemm_nt_res_stats": lambda lda, ldw: (p, lda, p, ldw, p, p, n, p, p, m, n, k, HGR_F16, 0),
+               "hgr_gemm_nt_res_stats_guard": lambda lda, ldw: (p, lda, p, ldw, p, p, n, p, p, 1.0, p, m, n, k, HGR_F16, 0),
+               "hgr_gemm_nt_bias_gelu_dual": lambda lda, ldw: (p, lda, p, ldw, p, n, p, n, p, m, n, k, HGR_F16, 0),
+               "hgr_gemm_nt_qgelu_grad_colsum": lambda lda, ldw: (p, lda, p, ldw, p, n, p, n, p, m, n, k, HGR_F16, 0)}
+    for name, args in entries.items():
+        plan = ops.gemm_plan(lambda: _lib.call(name, *args(la - 8, lw - 8)))             # one step below: planned on gemm_nt_duo
+        assert [d["kernel"] for d in plan] == [3], (name, plan)
+        for lda, ldw in ((la, k), (k, lw)):
+            with pytest.raises(_lib.HgrError, match="beyond 4 GB"):
+                _lib.call(name, *args(lda, ldw))
+    assert ops.gelu_dual_ok(m, n, k, la - 8, lw - 8) and not ops.gelu_dual_ok(m, n, k, la, k) and not ops.gelu_dual_ok(m, n, k, k, lw)
+
+    # hgr_gemm_nt_ln_mha is outside the capture: it would launch.  Its dtype check comes after the 4 GB check, so a bad dtype tells the
+    # two sides of the limit apart without a launch: "bad dtype" = the operand sizes were accepted.
+    b, l, heads = 16, 64, 2                                            # 1024 rows of width 128, in_proj weight [384, 128]
+    w = heads * 64
+    lw3 = limit(3 * w)
+    mha = lambda ldx, ldw: _lib.call("hgr_gemm_nt_ln_mha", p, ldx, p, ldw, p, p, p, 1e-5, p, w, b, l, heads, 0, 7, 0)
+    with pytest.raises(_lib.HgrError, match="bad dtype"):
+        mha(la - 8, lw3 - 8)
+    for ldx, ldw in ((la, w), (w, lw3)):
+        with pytest.raises(_lib.HgrError, match="beyond 4 GB"):
+            mha(ldx, ldw)
+    assert ops.ln_mha_ok(w, l, rows=b * l, ldx=la - 8) and not ops.ln_mha_ok(w, l, rows=b * l, ldx=la)
+    assert lib.hgr_gemm_plan_capture(None, 0) == 0
+
+
 def test_product_library_has_no_ablation_switches():
     """Round-5 verdict, hygiene: the wrong-result ablation switches (parts of a kernel left out for timing experiments) exist in
     `make lab` builds only.  The product library must not even contain their environment-variable names, and the lab-only entry
