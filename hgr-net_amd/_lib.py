@@ -104,6 +104,8 @@ SIGNATURES = {
     "hgr_gemm_nt_bias_gelu_dual": [_p, _l, _p, _l, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p],
     "hgr_gemm_nt_qgelu_grad_colsum": [_p, _l, _p, _l, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p],
     "hgr_vit_embed_ln_stats": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p],
+    "hgr_vit_patch_embed_ln_ok": [_i, _i, _i, _i, _i],
+    "hgr_vit_patch_embed_ln": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p],
     "hgr_row_stats16": [_p, _p, _p, _p, _i, _i, _i, _p],
     "hgr_pair_rows_f32": [_p, _p, _p, _i, _i, _l, _p, _i, _p],
     "hgr_logits_eval_workspace_bytes": [_i, _i],

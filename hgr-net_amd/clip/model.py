@@ -181,6 +181,7 @@ IMG_STREAMS_MIN_ROWS = 8192
 CLS_LAST = os.environ.get("HGR_CLS_LAST", "1") != "0"      # HGR_CLS_LAST=0: the last image block runs out_proj / MLP on every token (A/B runs, tests)
 LN_FUSED = os.environ.get("HGR_LN_FUSED", "1") != "0"     # HGR_LN_FUSED=0: separate LayerNorm launches (the first build's path), for A/B runs
 QKV_MHA = os.environ.get("HGR_QKV_MHA", "1") != "0"       # HGR_QKV_MHA=0: the in_proj GEMM writes qkv and hgr_mha reads it back (two launches)
+PATCH_FUSED = os.environ.get("HGR_PATCH_FUSED", "1") != "0"   # HGR_PATCH_FUSED=0: im2col -> patch GEMM -> embed + ln_pre as three launches (A/B runs, tests)
 
 
 def ln_fusable(w: int, m: int = 0) -> bool:
@@ -600,20 +601,27 @@ class CLIP(nn.Module):
         ps = v.patch_size
         g = r // ps
         gg, l, w = g * g, g * g + 1, v.conv1.weight.shape[0]
-        patches = ws.get(tag + ".patches", (b * gg, p["kp"]), dt, dev)
-        if u8:
-            ops.im2col_patches_u8(image, patches, ps)
-        else:
-            ops.im2col_patches(image, patches, ps)
-        pe = ws.get(tag + ".pe", (b * gg, w), torch.float32, dev)
-        ops.gemm_nt(patches, p["conv_w_nhwc"] if u8 else p["conv_w"], pe, tag="patch")
-        cls16 = ws.get(tag + ".cls16", (b, w), dt, dev)
         fused = ln_fusable(w, b * l) and "v" not in self._ln_off
+        # pixels -> residual pair in one launch (hgr_vit_patch_embed_ln): no unfolded patch matrix, no fp32 patch embedding
+        one_launch = (PATCH_FUSED and fused and not u8 and image.dtype == torch.float32 and image.is_contiguous() and p["kp"] == 3 * ps * ps
+                      and ops.vit_patch_embed_ln_ok(b, r, ps, w, dt))
+        if not one_launch:
+            patches = ws.get(tag + ".patches", (b * gg, p["kp"]), dt, dev)
+            if u8:
+                ops.im2col_patches_u8(image, patches, ps)
+            else:
+                ops.im2col_patches(image, patches, ps)
+            pe = ws.get(tag + ".pe", (b * gg, w), torch.float32, dev)
+            ops.gemm_nt(patches, p["conv_w_nhwc"] if u8 else p["conv_w"], pe, tag="patch")
+        cls16 = ws.get(tag + ".cls16", (b, w), dt, dev)
         if fused:
             xh = ws.get(tag + ".xh", (b * l, w), dt, dev)
             xl = ws.get(tag + ".xl", (b * l, w), ops.PAIR_LO, dev)
             stats = ws.get(tag + ".stats", (b * l, w // 64, 2), torch.float32, dev)
-            ops.vit_embed_ln_stats(pe, p["cls"], p["pos"], p["ln_pre"][0], p["ln_pre"][1], xh, xl, stats, b, gg)
+            if one_launch:
+                ops.vit_patch_embed_ln(image, p["conv_w"], p["cls"], p["pos"], p["ln_pre"][0], p["ln_pre"][1], xh, xl, stats, ps)
+            else:
+                ops.vit_embed_ln_stats(pe, p["cls"], p["pos"], p["ln_pre"][0], p["ln_pre"][1], xh, xl, stats, b, gg)
             if taps is not None:
                 taps["visual.ln_pre"] = ops.pair_value(xh, xl).view(b, l, w)
             _run_blocks(None, p["vblocks"], w // 64, b, l, False, dt, ws, tag, taps, "visual.transformer", (xh, xl), stats, self._ln_flag("v", dev),

@@ -229,6 +229,57 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
+// ---- one row of the ViT token assembly + ln_pre (clip/model.py:223-225): ONE copy of the text for vit_embed_ln (hgr_norm.hip) and
+// the one-launch patch embedding (hgr_patch_embed.hip), so that both round alike ------------------------------------------------------
+// One wave owns the row: the lane holds v[i] = columns 4 (64 i + lane) .. + 3 of (source + positional embedding) and s = the lane's
+// sum of them.  Two-pass statistics (mean, then centred second moment), gamma / beta, then the row leaves as fp32 (x) or, with STATS
+// (the first block's LayerNorm is folded into its QKV GEMM, hgr_gemm_nt_ln), as the 16-bit pair (hi, lo), x = hi + lo, + the (sum, sum
+// of squares) of every 64-column slot = one DPP row of 16 lanes per slot (W % 64 == 0).
+// The text is a macro over the names NV, DT, STATS, v, s, lane, nv, W, eps, gamma, beta, x, row, xh, xl, stats because vit_embed_ln
+// must keep its instructions: the same statements behind a function call compile to the same arithmetic in another register and
+// branch order (`make devasm` differs), expanded in place they compile to the kernel as it was.  vit_ln_row() is the function form.
+#define HGR_VIT_LN_ROW_BODY \
+    const float mean = wave_sum(s) / (float)W; \
+    float q = 0.f; \
+_Pragma("unroll") \
+    for (int i = 0; i < NV; ++i) { \
+        const int c = i * 64 + lane; \
+        if (i * 64 < nv && c < nv) { \
+_Pragma("unroll") \
+            for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; q += d * d; } \
+        } \
+    } \
+    const float rstd = rsqrtf(wave_sum(q) / (float)W + eps); \
+    const f32x4 *gv = (const f32x4 *)gamma, *bv = (const f32x4 *)beta; \
+    f32x4 *out = STATS ? nullptr : (f32x4 *)(x + (int64_t)row * W); \
+_Pragma("unroll") \
+    for (int i = 0; i < NV; ++i) { \
+        const int c = i * 64 + lane; \
+        if (i * 64 < nv && c < nv) { \
+            const f32x4 ga = gv[c], be = bv[c]; \
+            f32x4 o; \
+_Pragma("unroll") \
+            for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * ga[e] + be[e]; \
+            if (!STATS) out[c] = o; \
+            if (STATS) { \
+                typename T16<DT>::vec4 nh; \
+                unsigned nl = 0u; \
+_Pragma("unroll") \
+                for (int e = 0; e < 4; ++e) { unsigned q; typename T16<DT>::elem h; pair_split<DT>(o[e], h, q); nh[e] = h; nl |= q << (8 * e); } \
+                ((typename T16<DT>::vec4 *)((typename T16<DT>::elem *)xh + (int64_t)row * W))[c] = nh; \
+                ((unsigned *)((unsigned char *)xl + (int64_t)row * W))[c] = nl; \
+                const float s1 = row16_sum((o[0] + o[1]) + (o[2] + o[3])); \
+                const float s2 = row16_sum((o[0] * o[0] + o[1] * o[1]) + (o[2] * o[2] + o[3] * o[3])); \
+                if ((lane & 15) == 0) *(float2 *)(stats + ((int64_t)row * (W >> 6) + (c >> 4)) * 2) = make_float2(s1, s2); \
+            } \
+        } \
+    }
+template <int NV, int DT, bool STATS>
+__device__ __forceinline__ void vit_ln_row(const f32x4 (&v)[NV], float s, int lane, int nv, int W, float eps, const float *gamma, const float *beta,
+                                           float *x, int row, void *xh, void *xl, float *stats) {
+    HGR_VIT_LN_ROW_BODY
+}
+
 // ---- host-side error plumbing -------------------------------------------------------------------
 int hgr_set_error(int code, const char *fmt, ...);
 

@@ -82,44 +82,7 @@ __global__ __launch_bounds__(256) void vit_embed_ln(const float *__restrict__ pa
             s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
         }
     }
-    const float mean = wave_sum(s) / (float)W;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        if (i * 64 < nv && c < nv) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; q += d * d; }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)W + eps);
-    const f32x4 *gv = (const f32x4 *)gamma, *bv = (const f32x4 *)beta;
-    f32x4 *out = STATS ? nullptr : (f32x4 *)(x + (int64_t)row * W);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        if (i * 64 < nv && c < nv) {
-            const f32x4 ga = gv[c], be = bv[c];
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * ga[e] + be[e];
-            if (!STATS) out[c] = o;
-            if (STATS) {
-                // the first block's LayerNorm is folded into its QKV GEMM (hgr_gemm_nt_ln): the row leaves as the 16-bit pair
-                // (hi, lo), x = hi + lo, the form the residual stream keeps between the GEMMs, + the (sum, sum of squares)
-                // of every 64-column slot = one DPP row of 16 lanes per slot (W % 64 == 0)
-                typename T16<DT>::vec4 nh;
-                unsigned nl = 0u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { unsigned q; typename T16<DT>::elem h; pair_split<DT>(o[e], h, q); nh[e] = h; nl |= q << (8 * e); }
-                ((typename T16<DT>::vec4 *)((typename T16<DT>::elem *)xh + (int64_t)row * W))[c] = nh;
-                ((unsigned *)((unsigned char *)xl + (int64_t)row * W))[c] = nl;
-                const float s1 = row16_sum((o[0] + o[1]) + (o[2] + o[3]));
-                const float s2 = row16_sum((o[0] * o[0] + o[1] * o[1]) + (o[2] * o[2] + o[3] * o[3]));
-                if ((lane & 15) == 0) *(float2 *)(stats + ((int64_t)row * (W >> 6) + (c >> 4)) * 2) = make_float2(s1, s2);
-            }
-        }
-    }
+    HGR_VIT_LN_ROW_BODY         // hgr_common.h: shared with the one-launch patch embedding
 }
 
 // x fp32 [rows, W] -> the 16-bit pair (hi, lo) + per-slot LayerNorm statistics (the form hgr_gemm_nt_res_stats keeps), for the

@@ -205,6 +205,30 @@ def vit_embed_ln_stats(patches, cls, pos, gamma, beta, xh, xl, stats, b, g, eps=
               b, g, xh.shape[1], eps, DT_OF[xh.dtype], _stream())
 
 
+def vit_patch_embed_ln_ok(b: int, r: int, patch: int, w: int, dtype) -> bool:
+    """Shape contract of hgr_vit_patch_embed_ln, asked of the library itself (hgr_vit_patch_embed_ln_ok: patch 32, at most 56 patches
+    per image, width 768, f16 / bf16).  Everything else keeps im2col_patches -> gemm_nt -> vit_embed_ln_stats."""
+    code = DT_OF.get(dtype, dtype if isinstance(dtype, int) else -1)
+    return bool(_lib.load().hgr_vit_patch_embed_ln_ok(int(b), int(r), int(patch), int(w), int(code)))
+
+
+def vit_patch_embed_ln(image: torch.Tensor, conv_w: torch.Tensor, cls, pos, gamma, beta, xh, xl, stats, patch: int, eps=1e-5) -> None:
+    """fp32 NCHW pixels -> the pair (xh, xl) + slot statistics of ln_pre(tokens), one launch (hgr_vit_patch_embed_ln): the bits of
+    im2col_patches -> gemm_nt (fp32 out) -> vit_embed_ln_stats.  Recorded for PROFILE as the patch GEMM with the bytes it really moves."""
+    assert image.dtype == torch.float32 and image.dim() == 4 and image.shape[1] == 3 and image.shape[2] == image.shape[3] and image.is_contiguous()
+    b, r = image.shape[0], image.shape[2]
+    w, k = conv_w.shape
+    gg = (r // patch) ** 2
+    assert conv_w.is_contiguous() and k == 3 * patch * patch and conv_w.dtype == xh.dtype and xl.dtype == PAIR_LO
+    assert xh.is_contiguous() and xl.is_contiguous() and xh.shape == xl.shape == (b * (gg + 1), w)
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() >= b * (gg + 1) * (w // 64) * 2
+    ev = _prof_begin()
+    _lib.call("hgr_vit_patch_embed_ln", _dev(image), _dev(conv_w), _dev(cls), _dev(pos), _dev(gamma), _dev(beta), _dev(xh), _dev(xl), _dev(stats),
+              b, r, patch, w, eps, DT_OF[xh.dtype], _stream())
+    rows = b * (gg + 1)
+    _prof_end(ev, 2.0 * b * gg * w * k, 4 * b * 3 * r * r + 2 * w * k + 3 * rows * w + 8 * rows * (w // 64), "patch")
+
+
 def row_stats16(x: torch.Tensor, xh: torch.Tensor, xl: torch.Tensor, stats: torch.Tensor) -> None:
     assert x.dtype == torch.float32 and x.is_contiguous() and xh.is_contiguous() and xl.is_contiguous() and xh.shape == xl.shape == x.shape
     assert xl.dtype == PAIR_LO and stats.numel() >= x.shape[0] * (x.shape[1] // 64) * 2

@@ -759,6 +759,18 @@ int hgr_gemm_nt_qgelu_grad_colsum(const void *A, int64_t lda, const void *W, int
 int hgr_vit_embed_ln_stats(const float *patches, const float *class_embedding, const float *positional_embedding,
                            const float *gamma, const float *beta, void *xh, void *xl, float *stats,
                            int B, int G, int W, float eps, int dtype, void *stream);
+/*
+ * The front of a ViT-B/32 tower in one launch (clip/model.py:219-226: x = conv1(x) as a GEMM over the patches; class token in front;
+ * + positional_embedding; ln_pre): fp32 NCHW pixels image [B, 3, R, R] and conv_w [W, 3 * P * P] (16-bit, K order (c, py, px)) to the
+ * pair xh / xl [B * (gg + 1), W] and stats [B * (gg + 1), W / 64, 2], gg = (R / P)^2 - the three tensors, bit for bit, that
+ * hgr_im2col_patches -> hgr_gemm_nt (fp32 out) -> hgr_vit_embed_ln_stats write, without the unfolded patch matrix and the fp32 patch
+ * embedding in memory.  One workgroup per two images.  Supported (hgr_vit_patch_embed_ln_ok returns 1; everything else is rejected
+ * with HGR_EINVAL and keeps the three-launch chain): P = 32, R % 32 == 0, gg <= 56, W = 768, f16 or bf16; operands 16-byte aligned.
+ */
+int hgr_vit_patch_embed_ln_ok(int B, int R, int P, int W, int dtype);
+int hgr_vit_patch_embed_ln(const float *image, const void *conv_w, const float *class_embedding, const float *positional_embedding,
+                           const float *gamma, const float *beta, void *xh, void *xl, float *stats,
+                           int B, int R, int P, int W, float eps, int dtype, void *stream);
 /* x fp32 [rows, W] -> pair + slot statistics (text tower: embedding rows feed the first block) */
 int hgr_row_stats16(const float *x, void *xh, void *xl, float *stats, int rows, int W, int dtype, void *stream);
 /* out fp32 [rows, W] (compact) = xh[src] + xl[src], src = i * row_mul + (row_idx ? row_idx[i] : 0): selected rows of the pair back in
