@@ -1,3 +1,1 @@
-from .dgp import GCN_Dense_Att, GraphConv, GraphOperator, fold_groups, group_edges
-
-__all__ = ["GCN_Dense_Att", "GraphConv", "GraphOperator", "fold_groups", "group_edges"]
+from .dgp import DGPTrainer, GCN_Dense_Att, GraphConv, GraphOperator, dropout_keep, fold_groups, group_edges

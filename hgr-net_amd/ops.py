@@ -1098,6 +1098,53 @@ def csr_group_aggregate(support: torch.Tensor, op, att: torch.Tensor, bias: Opti
     return out
 
 
+def csr_group_att_grad(support: torch.Tensor, op, bias: Optional[torch.Tensor], g: torch.Tensor, y: Optional[torch.Tensor],
+                       dout: Optional[torch.Tensor], p: torch.Tensor, slope: float = 0.2) -> torch.Tensor:
+    """DGP backward gather: dout[i] = g[i] * (y[i] > 0 ? 1 : slope) (y None: g is dO already) and the attention gradient's rows
+    p[i, d] = dout[i] . sum_{e in (i, d)} inv_e (support[col_e] + bias); da = colsum(p).  dout may alias g."""
+    assert support.dtype == g.dtype == p.dtype == torch.float32 and support.stride(1) == 1 and g.stride(1) == 1
+    assert support.shape[0] == g.shape[0] == op.n and support.shape == g.shape and p.shape == (op.n, op.D) and p.is_contiguous()
+    for t in (y, dout):
+        assert t is None or (t.dtype == torch.float32 and t.stride(1) == 1 and t.shape == g.shape)
+    assert y is None or dout is not None
+    c = support.shape[1]
+    _lib.call("hgr_csr_group_att_grad", _dev(support), support.stride(0), _dev(bias), _dev(g), g.stride(0), _dev(y),
+              y.stride(0) if y is not None else 0, _dev(dout), dout.stride(0) if dout is not None else 0, _dev(op.item_row), _dev(op.item_e0),
+              _dev(op.item_e1), _dev(op.item_slot), op.item_row.numel(), _dev(op.col), _dev(op.inv_deg), _dev(op.grp), op.D,
+              _dev(op.split_row), _dev(op.split_slot0), _dev(op.split_n), op.split_row.numel(), _dev(op.partial_groups()), _dev(p), c, slope, _stream())
+    return p
+
+
+def dgp_loss_head(o: torch.Tensor, rows: torch.Tensor, f: torch.Tensor, loss_rows: torch.Tensor, loss: torch.Tensor, dout: torch.Tensor) -> torch.Tensor:
+    """Masked L2 loss of the DGP trainer on F.normalize(o) and its gradient with respect to o (hgr_dgp_loss_head); `rows` int32, distinct
+    (the caller checks: a duplicate would make two workgroups write one row of dout).  The loss stays on the device."""
+    assert o.dtype == f.dtype == dout.dtype == loss_rows.dtype == loss.dtype == torch.float32 and rows.dtype == torch.int32
+    assert o.stride(1) == 1 and f.stride(1) == 1 and dout.stride(1) == 1 and rows.is_contiguous() and o.shape == dout.shape
+    n_t = rows.numel()
+    assert f.shape == (n_t, o.shape[1]) and loss_rows.numel() >= n_t and loss.numel() >= 1
+    _lib.call("hgr_dgp_loss_head", _dev(o), o.stride(0), _dev(rows), _dev(f), f.stride(0), n_t, o.shape[0], _dev(loss_rows), _dev(loss),
+              _dev(dout), dout.stride(0), o.shape[1], _stream())
+    return loss
+
+
+def dropout_counter(x: torch.Tensor, y: torch.Tensor, seed: int, step: int, layer: int) -> torch.Tensor:
+    """y = x * keep * 2 with keep = baseline.dgp.dropout_keep(seed, step, layer, rows, cols): counter-based, nothing stored; y may be x."""
+    assert x.dtype == y.dtype == torch.float32 and x.dim() == 2 and x.shape == y.shape and x.stride(1) == 1 and y.stride(1) == 1
+    seed &= 0xFFFFFFFF
+    _lib.call("hgr_dropout_counter", _dev(x), x.stride(0), _dev(y), y.stride(0), x.shape[0], x.shape[1],
+              seed - (1 << 32) if seed >> 31 else seed, step, layer, _stream())
+    return y
+
+
+def adam_l2(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, betas=(0.9, 0.999), eps: float = 1e-8,
+            wd: float = 0.0) -> None:
+    """torch.optim.Adam step with coupled weight decay (hgr_adam_l2) on one fp32 tensor."""
+    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
+    assert p.dtype == g.dtype == m.dtype == v.dtype == torch.float32 and p.numel() == g.numel() == m.numel() == v.numel()
+    WEIGHTS_GEN[0] += 1
+    _lib.call("hgr_adam_l2", _dev(p), _dev(g), _dev(m), _dev(v), p.numel(), lr, betas[0], betas[1], eps, wd, step, _stream())
+
+
 def dot_f32(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, alpha: float = 1.0, accumulate: bool = False) -> torch.Tensor:
     """out[0] (+)= alpha * sum(a * b) for contiguous fp32 tensors of equal size."""
     assert a.dtype == b.dtype == out.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()

@@ -628,6 +628,54 @@ int hgr_csr_group_aggregate(const float *support, int64_t ld_support, const int 
                             float *partial, float *out, int64_t ld_out, int C, float slope, int normalize, void *stream);
 
 /*
+ * DGP baseline training (baseline/DGP/train_gcn_dense_att.py:96-102: forward, masked utils.l2_loss, backward, Adam).  With
+ * a = softmax(att), S = Xd W and O[i] = sum_e a[grp_e] inv_e (S[col_e] + b) the backward of one layer side is
+ *     dO    = G * (Y > 0 ? 1 : slope)               (hidden layer; the slope applies at 0, as torch's LeakyReLU backward does)
+ *     da_d  = sum_i dO[i] . sum_{e in (i, d)} inv_e (S[col_e] + b)            datt = a o (da - a . da)
+ *     T[j]  = sum_{e: col_e = j} a[grp_e] inv_e dO[row_e]      = hgr_csr_group_aggregate on the transposed CSR (bias NULL, slope 1)
+ *     db = colsum(T),  dW = Xd^T T,  dXd = T W^T
+ *
+ * hgr_csr_group_att_grad: per row, dO[i] (written to dout; y NULL: g IS dO, dout may be NULL or receive a copy; dout may alias g)
+ * and P[i, d] = dO[i] . sum_{e in (i, d)} inv_e (S[col_e] + b), P fp32 [n, D] with every entry written; da = colsum(P)
+ * (hgr_colsum).  The CSR's edges must be sorted by (row, group) so that a group is one run of a row; same work-item and
+ * split tables as hgr_csr_group_aggregate, `partial` fp32 [n_slots, D].  bias may be NULL.  C % 4 == 0, C <= 4096.  No atomics.
+ */
+int hgr_csr_group_att_grad(const float *support, int64_t ld_support, const float *bias, const float *g, int64_t ld_g,
+                           const float *y, int64_t ld_y, float *dout, int64_t ld_dout, const int *item_row,
+                           const int *item_e0, const int *item_e1, const int *item_slot, int n_items, const int *col,
+                           const float *inv_deg, const unsigned char *grp, int D, const int *split_row,
+                           const int *split_slot0, const int *split_n, int n_split, float *partial, float *P, int C,
+                           float slope, void *stream);
+
+/*
+ * Loss head on the un-normalised last layer O [n, ld_o]: for the n_t DISTINCT rows[k], Y = O / max(|O|, 1e-12) (F.normalize,
+ * gcn_dense_att.py:116), loss_rows[k] = |Y[rows[k]] - F[k]|^2 / (2 n_t) (utils.l2_loss), *loss = their sum in a fixed order,
+ * and dout [n, ld_dout] = dL/dO: (Gy - Y (Y . Gy)) / max(|O|, 1e-12) with Gy = (Y - F[k]) / n_t on the selected rows, 0 elsewhere
+ * (the whole buffer is cleared first).  F fp32 [n_t, ld_f].  C % 4 == 0, C <= 4096.
+ */
+int hgr_dgp_loss_head(const float *O, int64_t ld_o, const int *rows, const float *F, int64_t ld_f, int n_t, int n,
+                      float *loss_rows, float *loss, float *dout, int64_t ld_dout, int C, void *stream);
+
+/*
+ * Counter-based dropout (p = 0.5, nn.Dropout of gcn_dense_att.py:18): y[r, c] = x[r, c] * keep * 2, y may alias x.  With
+ * fmix32 = murmur3's 32-bit finaliser and 32-bit wrap-around arithmetic,
+ *     key  = fmix32(seed + 0x9E3779B9 * (step + 1));   key = fmix32(key ^ (layer * 0x85EBCA6B + 0xC2B2AE35))
+ *     keep = fmix32((r * C + c) ^ key) >> 31
+ * - a function of (seed, step, layer, element index) only, not of strides or of the launch: the backward calls the same entry
+ * on the gradient, no mask is stored.  Not torch's generator.  C % 4 == 0, rows * C < 2^32.
+ */
+int hgr_dropout_counter(const float *x, int64_t ld_x, float *y, int64_t ld_y, int rows, int C, int seed, int step, int layer,
+                        void *stream);
+
+/*
+ * torch.optim.Adam (train_gcn_dense_att.py:80) on fp32 parameters: g' = g + wd p (coupled decay, seen by both moments),
+ * m = m + (g' - m)(1 - beta1), v = beta2 v + (1 - beta2) g'^2, p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps).
+ * hgr_adamw is the decoupled, clipping optimiser of the CLIP path.
+ */
+int hgr_adam_l2(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps, float wd,
+                int step, void *stream);
+
+/*
  * Row-wise softmax cross-entropy (nn.CrossEntropyLoss at clip_tree.py:49,275): loss_rows[r] = lse(logits[r]) -
  * logits[r, labels[r]]; dlogits (optional) = (softmax - onehot) * gscale (gscale = weight / rows for the mean).
  */
