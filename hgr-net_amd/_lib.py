@@ -81,6 +81,7 @@ SIGNATURES = {
     "hgr_hedge_counters_rows": [_p, _i, _p, _p, _p, _i, _p, _i, _p],
     "hgr_set_ranks": [_p, _l, _i, _p, _p, _i, _p, _p, _p, _i, _p],
     "hgr_set_counters_rows": [_p, _p, _i, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p],
+    "hgr_dgp_score_rows": [_p, _l, _i, _i, _i, _f, _p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _p],
     "hgr_dot_f32":[_p, _p, _l, _p, _f, _i, _p],
     "hgr_conv3x3_nhwc_plain": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "hgr_gemm_nt_splitk": [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p],

@@ -2,6 +2,7 @@
 device trainer (`dgp.DGPTrainer`).  Same options, same printed line, same files (`epoch_K.pth` = the state dict in the
 reference's schema, `epoch_K.pred` = {'wnids', 'pred'}, `trlog`); the three material files are options here, and
 `--synthetic N` trains on a generated graph with random vectors and targets where the material files are absent.
+`--eval-after` scores the final predictions in memory with evaluate_dgp's options (`--features`, `--test-set`, ...).
 
 Row convention.  The reference builds `fc_vectors[k] = fc_vector[wnids.index(train_wnids[k])]`, shuffles `tlist = range(len(
 fc_vectors))` and compares `output_vectors[tlist[:n_train]]` with `fc_vectors[tlist[:n_train]]`: target k is matched to OUTPUT
@@ -39,7 +40,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     parser.add_argument("--seed", type=int, default=0, help="dropout counter seed, parameter initialisation and the train / val shuffle")
     parser.add_argument("--synthetic", type=int, default=None, metavar="N",
                         help="train on a generated N-node graph (synth.make_dag) with random vectors and targets instead of the material files")
-    return parser.parse_args(argv)
+    parser.add_argument("--eval-after", action="store_true",
+                        help="score the final predictions in memory like evaluate_dgp (its options below; with --synthetic on generated features)")
+    from .evaluate_dgp import add_eval_options, check_args
+    add_eval_options(parser.add_argument_group("scoring (--eval-after)"), standalone=False)
+    args = parser.parse_args(argv)
+    check_args(args)
+    return args
 
 
 def split_trainval(n_trainval: int, trainval: str, seed: int) -> Tuple[List[int], List[int]]:
@@ -58,11 +65,17 @@ def fc_targets(wnids: Sequence[str], fcfile, train_wnids: Sequence[str]) -> torc
     return torch.tensor([fc_vector[pos[w]] for w in train_wnids], dtype=torch.float32)
 
 
+def synthetic_dag(n_nodes: int, seed: int):
+    """The edge list [[parent, child], ...] the synthetic material is generated from."""
+    from .. import synth
+    return synth.make_dag(n_nodes, 10, seed=7 + seed, multi_parent=0.03)
+
+
 def synthetic_material(n_nodes: int, seed: int, dim_in: int = 300, dim_out: int = 512):
     """(graph, fcfile, splits) in the formats of the three material files, from synth.make_dag."""
     from .. import synth
     from . import dgp
-    dag = synth.make_dag(n_nodes, 10, seed=7 + seed, multi_parent=0.03)
+    dag = synthetic_dag(n_nodes, seed)
     wnids = ["fall11"] + sorted({w for e in dag for w in e} - {"fall11"})
     idx = {w: i for i, w in enumerate(wnids)}
     n = len(wnids)
@@ -123,6 +136,25 @@ def main(argv=None) -> None:
             pred_obj = None if args.no_pred else {"wnids": wnids, "pred": gcn.eval()(word_vectors)}
             torch.save(gcn.state_dict(), osp.join(args.save_path, "epoch_{}.pth".format(epoch)))
             torch.save(pred_obj, osp.join(args.save_path, "epoch_{}.pred".format(epoch)))
+    if args.eval_after:
+        eval_after(args, wnids, gcn.eval()(word_vectors), splits)
+
+
+def eval_after(args: argparse.Namespace, wnids: Sequence[str], vectors: torch.Tensor, splits: dict) -> dict:
+    """Score the predictions in memory: evaluate_dgp's run on {'wnids', 'pred'} without the file in between."""
+    from . import dgp_eval, evaluate_dgp
+    pred = {"wnids": list(wnids), "pred": vectors.detach().to(torch.float32).cpu()}
+    if args.synthetic is not None:
+        graph_edges = synthetic_dag(args.synthetic, args.seed)
+        splits = {k: [w for w in v if w != "fall11"] for k, v in splits.items()}       # the synthetic splits draw from the root too
+        test = list(splits[args.test_set])
+        features = evaluate_dgp.synthetic_features(dgp_eval.pick_vectors(pred, test), test, args.seed)
+    else:
+        if args.features is None:
+            raise SystemExit("--eval-after needs --features FILE.npz")
+        graph_edges = json.load(open(args.graph_path, "r"))
+        features = dgp_eval.load_features(args.features)
+    return evaluate_dgp.run(args, graph_edges, splits, pred, features)
 
 
 if __name__ == "__main__":

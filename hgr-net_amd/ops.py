@@ -787,6 +787,39 @@ def set_counters_rows(rank: torch.Tensor, top1: torch.Tensor, targets: torch.Ten
               _dev(anc_levels), anc_ptr.numel() - 1, _dev(table), rank.shape[0], _stream())
 
 
+def dgp_mask_value(value: float, dtype: torch.dtype) -> float:
+    """`value` as a table of `dtype` stores it: the reference's `table[:, :n] = 1e-7` on an fp16 table writes 2^-23."""
+    return float(torch.tensor(value, dtype=torch.float64).to(dtype))
+
+
+def dgp_score_rows(table: torch.Tensor, depth: torch.Tensor, n_levels: int, n_masked: int = 0, mask_value: float = 1e-7,
+                   targets: Optional[torch.Tensor] = None, target: int = 0, n_cols: Optional[int] = None, k_pred: int = 0, out=None):
+    """(rank [rows], top1 [rows, 1], lv [rows, n_levels], pred [rows, k_pred] or None), all int32, of hgr_dgp_score_rows (definition
+    in include/hgr.h): the DGP scoring of one classifier-product table, fp16 or fp32 [rows, >= n_cols] with unit column stride (a view
+    of a wider buffer is fine).  The first `n_masked` columns read as `mask_value` rounded to the table's type; ``targets`` int64
+    [rows], or one ``target`` for every row; ``out`` = the four tensors of an earlier call, to be written again."""
+    assert table.dim() == 2 and table.dtype in (torch.float16, torch.float32) and table.stride(1) == 1
+    assert depth.dtype == torch.int32 and depth.is_contiguous()
+    rows = table.shape[0]
+    nc = table.shape[1] if n_cols is None else n_cols
+    assert 1 <= nc <= table.shape[1] and depth.numel() >= nc
+    assert targets is None or (targets.dtype == torch.int64 and targets.is_contiguous() and targets.numel() == rows)
+    dev = table.device
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.int32, device=dev), torch.empty((rows, 1), dtype=torch.int32, device=dev),
+               torch.empty((rows, n_levels), dtype=torch.int32, device=dev),
+               torch.empty((rows, k_pred), dtype=torch.int32, device=dev) if k_pred else None)
+    rank, top1, lv, pred = out
+    assert rank.dtype == top1.dtype == lv.dtype == torch.int32 and rank.numel() == rows and top1.numel() == rows
+    assert lv.shape == (rows, n_levels) and rank.is_contiguous() and top1.is_contiguous() and lv.is_contiguous()
+    assert (pred is None) == (k_pred == 0) and (pred is None or (pred.dtype == torch.int32 and pred.shape == (rows, k_pred) and pred.is_contiguous()))
+    # the sizes go to the library as they are: it rejects what hgr.h lists, before anything is launched
+    _lib.call("hgr_dgp_score_rows", _dev(table), table.stride(0), 1 if table.dtype == torch.float32 else 0, nc, n_masked,
+              dgp_mask_value(mask_value, table.dtype), _dev(depth), n_levels, _dev(targets), int(target), _dev(rank), _dev(top1), _dev(lv),
+              _dev(pred), k_pred, rows, _stream())
+    return rank, top1, lv, pred
+
+
 # ---- ModifiedResNet (RN) tower -------------------------------------------------------------------
 def conv3x3_nhwc(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, b: int, h: int, wd: int, c: int,
                  stride: int = 1) -> torch.Tensor:

@@ -409,6 +409,28 @@ int hgr_set_counters_rows(const int32_t *rank, const int32_t *top1, int n_sets, 
                           const int32_t *anc_ptr, const int32_t *anc_nodes, const int32_t *anc_levels, int n_nodes,
                           int64_t *table /* [n_sets][HGR_REPORT_MAXL + 1][HGR_SETS_COLS] */, int rows, void *stream);
 
+/* Scoring of DGP's predicted classifiers (the reference's baseline/DGP/evaluate_imagenet.py and evaluate_21kp.py, test_on_subset):
+ * one pass over every row of the classifier product `table` [rows, ld], fp16 (table_f32 = 0) or fp32 (1), not normalised.  With
+ *   v(c) = mask_value if c < n_masked else table[r, c]          (the reference's `table[:, :n] = 1e-7`, which its `copy.copy` alias
+ *                                                                 also puts into the values of the top-1 and of the level picks)
+ * and t = targets[r] (int64 [rows]) or `target` for every row when targets == NULL:
+ *   rank[r]  = #{c < n_cols : v(c) >= v(t)}   - the target counts itself, ties count AGAINST it, masking applies to the target too;
+ *              INT32_MAX when t lies outside [0, n_cols) (with targets == NULL such a target is rejected)
+ *   top1[r]  = the lowest c holding max_c v(c)
+ *   lv[r, l] = the lowest c holding max_c (depth[c] == l ? v(c) : -1): when every node of level l is below -1 the pick is the first
+ *              column outside the level, and a level with no column at all gives column 0 - hgr_level_argmax's rule
+ *   pred[r, j] (optional, int32 [rows, k_pred], k_pred <= 32; NULL with k_pred = 0) = t at j == rank[r] - 1, -1 elsewhere: the rank in
+ *              the shape hgr_eval_counters / hgr_eval_counters_rows take their hits from, so that with lv and top1 they advance the
+ *              reference's hits, `To`, `Path` and `Point` unchanged (rank <= k exactly when the target sits in the first k entries)
+ * depth int32 [n_cols], a value outside [0, n_levels) puts the column on no level; n_levels <= 32.  Compares are IEEE compares on the
+ * values (fp16 widened exactly): -0.0 ties with +0.0 and mask_value ties with a stored value equal to it; pass mask_value already
+ * rounded to the table's type (fp16(1e-7) = 2^-23).  NaN scores: unspecified outputs, but no address is ever made from a score.
+ * Exact integers that depend on no lane, wave or launch order.  One workgroup per row on a capped grid that loops over rows, 16-byte
+ * loads where the row's base allows them, per thread and level the best (value, column) as one 64-bit key in LDS. */
+int hgr_dgp_score_rows(const void *table, int64_t ld, int table_f32, int n_cols, int n_masked, float mask_value, const int32_t *depth,
+                       int n_levels, const int64_t *targets, int target, int32_t *rank, int32_t *top1, int32_t *lv, int32_t *pred,
+                       int k_pred, int rows, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * ModifiedResNet (RN50) tower, clip/model.py:93-150.  Activations are NHWC 16-bit ([B, H, W, C] =
  * a row-major [B*H*W, C] matrix), so every 1x1 convolution IS hgr_gemm_nt; inference BatchNorm
