@@ -101,6 +101,10 @@ SIGNATURES = {
     "hgr_dgp_loss_head": [_p, _l, _p, _p, _l, _i, _i, _p, _p, _p, _l, _i, _p],
     "hgr_dropout_counter": [_p, _l, _p, _l, _i, _i, _i, _i, _i, _p],
     "hgr_adam_l2": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p],
+    "hgr_cnzsl_std_chain_fwd": [_p, _l, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _i, _i, _i, _f, _f, _p],
+    "hgr_cnzsl_std_chain_bwd": [_p, _l, _p, _l, _p, _l, _p, _p, _p, _l, _p, _i, _i, _f, _p],
+    "hgr_bias_relu_f32": [_p, _l, _p, _p, _l, _i, _i, _p],
+    "hgr_relu_bwd_colsum_f32": [_p, _l, _p, _l, _p, _l, _p, _p, _i, _i, _p],
     "hgr_gemm_nt_res_stats": [_p, _l, _p, _l, _p, _p, _l, _p, _p, _i, _i, _i, _i, _p],
     "hgr_vit_head": [_p, _p, _l, _l, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p],
     "hgr_gemm_nt_res_stats_guard": [_p, _l, _p, _l, _p, _p, _l, _p, _p, _f, _p, _i, _i, _i, _i, _p],

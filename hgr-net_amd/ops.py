@@ -1178,6 +1178,62 @@ def adam_l2(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, 
     _lib.call("hgr_adam_l2", _dev(p), _dev(g), _dev(m), _dev(v), p.numel(), lr, betas[0], betas[1], eps, wd, step, _stream())
 
 
+# ---- CNZSL baseline (baseline/cnzsl.py) ------------------------------------------------------------------------------------------------
+CN_EPS = 1e-5                # ClassStandardization's epsilon, added to the VARIANCE (cnzsl.py:162)
+CN_MOMENTUM = 0.1            # running <- 0.9 running + 0.1 batch (cnzsl.py:165-166)
+CN_RESIDENT_ROWS = 2048      # hgr_cnzsl_std_chain_*: up to this many rows a 16-column strip stays in LDS
+RELU_BWD_CHUNK = 256         # hgr_relu_bwd_colsum_f32: rows per partial column sum
+
+
+def _f32_rows(*ts) -> bool:
+    return all(t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 for t in ts)
+
+
+def cnzsl_std_chain_fwd(z: torch.Tensor, bias: torch.Tensor, running, c: torch.Tensor, a: Optional[torch.Tensor] = None,
+                        stats: Optional[torch.Tensor] = None, train: bool = True, eps: float = CN_EPS, momentum: float = CN_MOMENTUM) -> torch.Tensor:
+    """Modules 2 (bias) .. 5 of CNZSLModel in one launch: c = cs(relu(cs(z + bias))).  `running` = (mean1, var1, mean2, var2), fp32
+    [H] each: updated in place with `train`, used as the statistics without.  Training also writes a = relu(cs(z + bias)) and
+    stats [4, H] = (m1, v1, m2, v2) for the backward; S >= 2 there (HgrError before any launch otherwise)."""
+    assert _f32_rows(z, c) and z.shape == c.shape and (a is None or (_f32_rows(a) and a.shape == z.shape))
+    s, h = z.shape
+    vecs = (bias,) + tuple(running)
+    assert len(vecs) == 5 and all(v.dtype == torch.float32 and v.is_contiguous() and v.numel() == h for v in vecs)
+    assert stats is None or (stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 4 * h)
+    _lib.call("hgr_cnzsl_std_chain_fwd", _dev(z), z.stride(0), *[_dev(v) for v in vecs], _dev(c), c.stride(0), _dev(a),
+              a.stride(0) if a is not None else 0, _dev(stats), s, h, 1 if train else 0, eps, momentum, _stream())
+    return c
+
+
+def cnzsl_std_chain_bwd(dc: torch.Tensor, a: torch.Tensor, z: torch.Tensor, bias: torch.Tensor, stats: torch.Tensor, dz: torch.Tensor,
+                        dbias: torch.Tensor, eps: float = CN_EPS) -> torch.Tensor:
+    """dz = d loss / d z and dbias = colsum(dz) of the training-mode chain, from dc and what the forward saved."""
+    assert _f32_rows(dc, a, z, dz) and dc.shape == a.shape == z.shape == dz.shape
+    s, h = z.shape
+    assert all(v.dtype == torch.float32 and v.is_contiguous() for v in (bias, stats, dbias)) and bias.numel() == dbias.numel() == h and stats.numel() == 4 * h
+    _lib.call("hgr_cnzsl_std_chain_bwd", _dev(dc), dc.stride(0), _dev(a), a.stride(0), _dev(z), z.stride(0), _dev(bias), _dev(stats),
+              _dev(dz), dz.stride(0), _dev(dbias), s, h, eps, _stream())
+    return dz
+
+
+def bias_relu_f32(x: torch.Tensor, bias: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = relu(x + bias) on fp32 rows; in place without `y`."""
+    y = x if y is None else y
+    assert _f32_rows(x, y) and x.shape == y.shape and bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == x.shape[1]
+    _lib.call("hgr_bias_relu_f32", _dev(x), x.stride(0), _dev(bias), _dev(y), y.stride(0), x.shape[0], x.shape[1], _stream())
+    return y
+
+
+def relu_bwd_colsum_f32(dy: torch.Tensor, y: torch.Tensor, dx: torch.Tensor, db: torch.Tensor, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx = dy [y > 0] (dx may be dy) and db = colsum(dx), deterministic; `scratch` fp32 [ceil(rows / 256) * C] beyond 256 rows."""
+    assert _f32_rows(dy, y, dx) and dy.shape == y.shape == dx.shape and db.dtype == torch.float32 and db.is_contiguous() and db.numel() == dy.shape[1]
+    rows, c = dy.shape
+    chunks = -(-rows // RELU_BWD_CHUNK)
+    assert chunks == 1 or (scratch is not None and scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= chunks * c)
+    _lib.call("hgr_relu_bwd_colsum_f32", _dev(dy), dy.stride(0), _dev(y), y.stride(0), _dev(dx), dx.stride(0), _dev(db), _dev(scratch),
+              rows, c, _stream())
+    return dx
+
+
 def dot_f32(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, alpha: float = 1.0, accumulate: bool = False) -> torch.Tensor:
     """out[0] (+)= alpha * sum(a * b) for contiguous fp32 tensors of equal size."""
     assert a.dtype == b.dtype == out.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()

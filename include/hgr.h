@@ -698,6 +698,41 @@ int hgr_adam_l2(float *p, const float *g, float *m, float *v, int64_t n, float l
                 int step, void *stream);
 
 /*
+ * CNZSL baseline (baseline/CNZSL/cnzsl.py:139-219): modules 2 (bias) .. 5 of the attribute -> prototype network in one launch.
+ * z fp32 [S, ld_z] = h1 W2^T, u = z + bias.  ClassStandardization as the reference has it: (x - mean_0(x)) / (var_0(x) + eps),
+ * UNBIASED variance (two-pass: the mean, then sum (x - mean)^2 / (S - 1)), divided by the variance itself.
+ *   train != 0 (S >= 2, else HGR_EINVAL before any launch):
+ *     m1, v1 of u;  a = relu((u - m1) / (v1 + eps));  m2, v2 of a;  c = (a - m2) / (v2 + eps);  stats [4, H] = (m1, v1, m2, v2);
+ *     running <- (1 - momentum) running + momentum batch, in place, for the four running vectors
+ *   train == 0 (S >= 1): the same with the running vectors in place of the batch statistics; nothing else is written; a may be NULL.
+ * A workgroup owns 16 columns and all rows; up to 2048 rows the strip is kept in LDS, beyond that it is re-read.  The summation
+ * order depends on S only.  H % 4 == 0; ld_* % 4 == 0 and >= H; operands 16-byte aligned.  No atomics.
+ */
+int hgr_cnzsl_std_chain_fwd(const float *z, int64_t ld_z, const float *bias, float *running_mean1, float *running_var1,
+                            float *running_mean2, float *running_var2, float *c, int64_t ld_c, float *a, int64_t ld_a,
+                            float *stats, int S, int H, int train, float eps, float momentum, void *stream);
+
+/*
+ * Backward of the training-mode chain: from dc = d loss / d c, the saved a, z, bias and stats, dz [S, ld_dz] = d loss / d z and
+ * dbias [H] = its column sums.  One standardisation with d = v + eps, xt = x - m:
+ *     dx_j = (g_j - mean(g)) / d - 2 xt_j (sum_i g_i xt_i) / ((S - 1) d^2)
+ * applied for layer 5, then the mask a > 0, then layer 3.  dz must not alias an input.  Same contract as the forward.
+ */
+int hgr_cnzsl_std_chain_bwd(const float *dc, int64_t ld_dc, const float *a, int64_t ld_a, const float *z, int64_t ld_z,
+                            const float *bias, const float *stats, float *dz, int64_t ld_dz, float *dbias, int S, int H,
+                            float eps, void *stream);
+
+/* y = relu(x + bias), fp32 [rows, C]; y may alias x.  C % 4 == 0, leading dimensions % 4 == 0, 16-byte aligned. */
+int hgr_bias_relu_f32(const float *x, int64_t ld_x, const float *bias, float *y, int64_t ld_y, int rows, int C, void *stream);
+
+/*
+ * dx = dy where y > 0, else 0 (dx may alias dy), and db [C] = the column sums of dx: per 256-row chunk in a fixed order, the
+ * chunks then added in order (scratch fp32 [ceil(rows / 256), C], unused up to 256 rows).  No atomics.
+ */
+int hgr_relu_bwd_colsum_f32(const float *dy, int64_t ld_dy, const float *y, int64_t ld_y, float *dx, int64_t ld_dx, float *db,
+                            float *scratch, int rows, int C, void *stream);
+
+/*
  * Row-wise softmax cross-entropy (nn.CrossEntropyLoss at clip_tree.py:49,275): loss_rows[r] = lse(logits[r]) -
  * logits[r, labels[r]]; dlogits (optional) = (softmax - onehot) * gscale (gscale = weight / rows for the mean).
  */
