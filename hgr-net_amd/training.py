@@ -44,6 +44,18 @@ def _pad64(n: int) -> int:
     return (n + 63) // 64 * 64
 
 
+def check_distinct_ids(id_lists) -> None:
+    """Every inner step's node ids must be distinct: its text-feature gradient goes back with hgr_rows_axpy, a plain ``+=`` per
+    destination row (include/hgr.h), so a node listed twice in one step would receive one of its two gradients, or a torn sum.
+    Host lists only: no device work, no sync."""
+    for j, ids in enumerate(id_lists):
+        seen = set()
+        for i in ids:
+            if i in seen:
+                raise ValueError(f"OMTrainer: inner step {j} lists node {i} twice (ids must be distinct: a duplicate row would receive two gradients)")
+            seen.add(i)
+
+
 def _grad(p: torch.nn.Parameter) -> torch.Tensor:
     if p.grad is None:
         p.grad = torch.zeros_like(p.data, dtype=torch.float32)
@@ -600,6 +612,7 @@ class OMTrainer:
         self.dp_group = dp
         if dp is not None:
             picks = self._agree_on_picks(picks, dp)
+        check_distinct_ids([ids for ids, _, _, _ in picks])    # before the text tower and the gather / scatter loop below
         self.last_contra = [(ids, pos) for ids, pos, _, _ in picks]
         uniq = sorted({i for ids, _, _, _ in picks for i in ids})
         where = {nid: j for j, nid in enumerate(uniq)}

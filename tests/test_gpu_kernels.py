@@ -881,14 +881,8 @@ def test_vit_embed_ln_stats_equals_unfused(dt):
 
 
 # ---- logits GEMM with the evaluation in its epilogue (hgr_logits_eval) --------------------------------------------------------
-@pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("case", ["n21841", "ragged_rows", "empty_level", "ties", "all_equal", "all_equal_wide", "clustered_test", "d1024"])
-def test_logits_eval_bit_exact_vs_gemm_plus_eval_rows(dt, case):
-    """hgr_logits_eval (no logits in memory: tile stage -> per-slice keys / maxima, row stage -> level arg-max, top-1, recomputed
-    candidates -> top-20) must give EXACTLY the ids of hgr_gemm_nt (fp32 logits) + hgr_eval_rows on the same operands
-    (main.py:136-176 on model/clip_tree.py:331): the full-size class matrix, ragged row counts, an empty level, exact ties
-    (duplicated class rows), all-equal logits (1 500 test elements reach the threshold: still the ranked path; `all_equal_wide`: 2 500,
-    more than the candidate list holds - the k-round fallback), a tiny clustered test set, D = 1024."""
+def _logits_eval_case(dt, case):
+    """Operands of one hgr_logits_eval case: 16-bit features and class matrix, the EvalIndex, (rows, n, k)."""
     rows, n, d, levels, k = 64, 3000, 256, 9, 20
     if case == "all_equal_wide":
         rows, n = 8, 5000
@@ -920,6 +914,18 @@ def test_logits_eval_bit_exact_vs_gemm_plus_eval_rows(dt, case):
         assert len(test) > 2048                               # LE_CAP: every test element reaches the threshold, the list overflows
     f16, z16 = f.to(dt).to(DEV), z.to(dt).to(DEV)
     index = ops.EvalIndex(torch.from_numpy(depth).to(DEV), torch.from_numpy(train).to(DEV), torch.from_numpy(test).to(DEV), levels)
+    return f16, z16, index, rows, n, k
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("case", ["n21841", "ragged_rows", "empty_level", "ties", "all_equal", "all_equal_wide", "clustered_test", "d1024"])
+def test_logits_eval_bit_exact_vs_gemm_plus_eval_rows(dt, case):
+    """hgr_logits_eval (no logits in memory: tile stage -> per-slice keys / maxima, row stage -> level arg-max, top-1, recomputed
+    candidates -> top-20) must give EXACTLY the ids of hgr_gemm_nt (fp32 logits) + hgr_eval_rows on the same operands
+    (main.py:136-176 on model/clip_tree.py:331): the full-size class matrix, ragged row counts, an empty level, exact ties
+    (duplicated class rows), all-equal logits (1 500 test elements reach the threshold: still the ranked path; `all_equal_wide`: 2 500,
+    more than the candidate list holds - the k-round fallback), a tiny clustered test set, D = 1024."""
+    f16, z16, index, rows, n, k = _logits_eval_case(dt, case)
     ld = (n + 63) // 64 * 64
     lg = torch.empty(rows, ld, dtype=torch.float32, device=DEV)
     ops.gemm_nt(f16, z16, lg, n=n)
@@ -931,6 +937,24 @@ def test_logits_eval_bit_exact_vs_gemm_plus_eval_rows(dt, case):
         assert torch.equal(w, g_), (case, name, int((w != g_).sum()))
     again = ops.logits_eval(f16, plan, k)
     assert all(torch.equal(a, b) for a, b in zip(got, again))           # run-to-run identical
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("case", ["ragged_rows", "ties"])
+def test_logits_eval_tile_stage_then_row_stage_equals_fused(dt, case):
+    """hgr_logits_eval_tile_stage + hgr_logits_eval_row_stage (the two launches the benchmark times on their own) together compute what
+    the fused call computes: the tile stage rewrites everything in the workspace that the row stage reads (the workspace is overwritten
+    with a byte pattern in between), and the row stage's level ids, top-1 and top-k are the fused call's bit for bit."""
+    f16, z16, index, rows, n, k = _logits_eval_case(dt, case)
+    plan = ops.LogitsEvalPlan(index).bind(z16)
+    want = [t.clone() for t in ops.logits_eval(f16, plan, k)]
+    ws = plan.workspace(rows, f16.device)
+    ws.fill_(0xA5)
+    ops.logits_eval(f16, plan, k, stage="tile")
+    assert plan.workspace(rows, f16.device) is ws                        # the same buffer goes to both stages
+    got = ops.logits_eval(f16, plan, k, stage="row")
+    for w, g_, name in zip(want, got, ("level arg-max", "top-1", "top-k")):
+        assert torch.equal(w, g_), (case, name, int((w != g_).sum()))
 
 
 def _logits_eval_oracle(lg: np.ndarray, depth: np.ndarray, train: np.ndarray, test: np.ndarray, n_levels: int, k: int):
