@@ -182,6 +182,24 @@ CLS_LAST = os.environ.get("HGR_CLS_LAST", "1") != "0"      # HGR_CLS_LAST=0: the
 LN_FUSED = os.environ.get("HGR_LN_FUSED", "1") != "0"     # HGR_LN_FUSED=0: separate LayerNorm launches (the first build's path), for A/B runs
 QKV_MHA = os.environ.get("HGR_QKV_MHA", "1") != "0"       # HGR_QKV_MHA=0: the in_proj GEMM writes qkv and hgr_mha reads it back (two launches)
 PATCH_FUSED = os.environ.get("HGR_PATCH_FUSED", "1") != "0"   # HGR_PATCH_FUSED=0: im2col -> patch GEMM -> embed + ln_pre as three launches (A/B runs, tests)
+# c_proj of the pair path on 320 x 256 tiles in one round (ops.gemm_nt_res_stats_wide): HGR_PROJ_WIDE=0 never (the 256 x 128 tile
+# launch), 1 by shape (_proj_wide_wanted), 2 wherever the library covers the shape (tests, A/B runs)
+PROJ_WIDE = {"0": 0, "2": 2}.get(os.environ.get("HGR_PROJ_WIDE", "1"), 1)
+_CUS: Dict[int, int] = {}
+
+
+def _proj_wide_wanted(m: int, n: int, k: int, dev: torch.device) -> bool:
+    """By shape: a long K (the tile's prologue and epilogue run beside nothing with one workgroup per compute unit) and enough
+    320 x 256 tiles to keep at least 7/8 of the compute units busy for the whole launch - ViT-B/32's c_proj at batch 512 is 240 tiles
+    of K = 3 072 on 256 units.  Measured on that batch (profiles/NOTES.md, "c_proj on 320 x 256 tiles"): c_proj 129.0 -> 116.3 us
+    back to back and the step 4.827 -> 4.745 ms; out_proj (K = 768, the same 240 tiles) 52.2 -> 53.2 us, which is why K counts."""
+    if PROJ_WIDE != 1:
+        return PROJ_WIDE == 2
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    cus = _CUS.get(idx)
+    if cus is None:
+        cus = _CUS[idx] = torch.cuda.get_device_properties(idx).multi_processor_count
+    return k >= 1024 and (m // 320) * (n // 256) * 8 >= 7 * cus
 
 
 def ln_fusable(w: int, m: int = 0) -> bool:
@@ -243,7 +261,11 @@ def _run_blocks(x: Optional[torch.Tensor], blocks, heads: int, b: int, l: int, c
                 break
             ops.gemm_nt_res_stats(att, k.w_out, xh, xl, k.b_out, stats, tag="out", flag=flag)
             ops.gemm_nt_ln(xh, k.wf_fc, u16, k.s_fc, k.c_fc, stats, k.eps2, quickgelu=True, tag="fc")
-            ops.gemm_nt_res_stats(u16, k.w_proj, xh, xl, k.b_proj, stats, tag="proj", flag=flag)
+            if (PROJ_WIDE and ops.gemm_nt_res_stats_wide_ok(m, w, 4 * w, u16.stride(0), k.w_proj.stride(0), xh.stride(0), dt)
+                    and _proj_wide_wanted(m, w, 4 * w, dev)):
+                ops.gemm_nt_res_stats_wide(u16, k.w_proj, xh, xl, k.b_proj, stats, tag="proj", flag=flag)
+            else:
+                ops.gemm_nt_res_stats(u16, k.w_proj, xh, xl, k.b_proj, stats, tag="proj", flag=flag)
             if taps is not None:
                 taps[f"{tap_prefix}.resblocks.{i}"] = ops.pair_value(xh, xl).view(b, l, w)
         return None

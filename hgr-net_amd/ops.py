@@ -130,6 +130,34 @@ def gemm_nt_res_stats(a: torch.Tensor, w: torch.Tensor, xh: torch.Tensor, xl: to
     _prof_end(ev, 2.0 * m * n * k, 2 * m * k + 2 * n * k + 6 * m * n + 8 * m * (n // 64), tag)     # pair: 3 bytes read + 3 written per element; slot statistics
 
 
+def gemm_nt_res_stats_wide_ok(m: int, n: int, k: int, lda: int, ldw: int, ldx: int, dtype) -> bool:
+    """Shape contract of hgr_gemm_nt_res_stats_wide, asked of the library itself (hgr_gemm_nt_res_stats_wide_ok: whole 320 x 256
+    tiles, at most one per compute unit, K % 128 == 0 and >= 256)."""
+    code = dtype if isinstance(dtype, int) else DT_OF.get(dtype, -1)
+    return bool(_lib.load().hgr_gemm_nt_res_stats_wide_ok(int(m), int(n), int(k), int(lda), int(ldw), int(ldx), int(code)))
+
+
+# launches of hgr_gemm_nt_res_stats_wide made through ops.gemm_nt_res_stats_wide (tests tell the two producer routes apart by it)
+WIDE_CALLS = [0]
+
+
+def gemm_nt_res_stats_wide(a: torch.Tensor, w: torch.Tensor, xh: torch.Tensor, xl: torch.Tensor, bias: torch.Tensor, stats: torch.Tensor,
+                           tag: str = "", flag: Optional[torch.Tensor] = None) -> None:
+    """gemm_nt_res_stats on 320 x 256 tiles, one workgroup per compute unit in one round (hgr_gemm_nt_res_stats_wide): the same bits
+    in xh, xl, stats and flag; shapes outside gemm_nt_res_stats_wide_ok are an error."""
+    m, k = a.shape
+    n = w.shape[0]
+    assert a.dtype == w.dtype == xh.dtype and xl.dtype == PAIR_LO and xh.shape == xl.shape == (m, n) and xh.stride() == xl.stride()
+    assert stats.dtype == torch.float32 and stats.numel() >= m * (n // 64) * 2 and a.stride(1) == w.stride(1) == xh.stride(1) == 1
+    assert flag is None or (flag.numel() == 1 and flag.element_size() == 4)
+    ev = _prof_begin()
+    _lib.call("hgr_gemm_nt_res_stats_wide", _dev(a), a.stride(0), _dev(w), w.stride(0), _dev(xh), _dev(xl), xh.stride(0), _dev(bias),
+              _dev(stats), LN_GUARD_SUMSQ if flag is not None else 0.0, _dev(flag), m, n, k, DT_OF[a.dtype], _stream())
+    if not _lib.muted():
+        WIDE_CALLS[0] += 1
+    _prof_end(ev, 2.0 * m * n * k, 2 * m * k + 2 * n * k + 6 * m * n + 8 * m * (n // 64), tag)     # as gemm_nt_res_stats
+
+
 def gemm_nt_bias_gelu_dual(a: torch.Tensor, w: torch.Tensor, pre: torch.Tensor, post: torch.Tensor, bias: torch.Tensor) -> None:
     """pre = a @ w^T + bias, post = QuickGELU(pre as rounded), both 16-bit, one launch (training forward of the MLP)."""
     assert a.dim() == 2 and w.dim() == 2 and a.dtype == w.dtype == pre.dtype == post.dtype and a.stride(1) == w.stride(1) == pre.stride(1) == post.stride(1) == 1

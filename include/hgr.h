@@ -820,6 +820,22 @@ int hgr_gemm_nt_res_stats_guard(const void *A, int64_t lda, const void *W, int64
                                 int M, int N, int K, int dtype, void *stream);
 
 /*
+ * The same product on 320 x 256 tiles, one 512-thread workgroup per tile and per CU in ONE round (csrc/hgr_gemm_wide.hip) - for
+ * launches whose tile count fills most of the chip without exceeding it, such as ViT-B/32's c_proj at batch 512 (25 600 x 768 x
+ * 3 072: 240 tiles), where the 256 x 128 tiles of hgr_gemm_nt_res_stats leave a tail round.  Same arguments and the same bits in xh,
+ * xl, stats and *flag as hgr_gemm_nt_res_stats_guard (flag = NULL: no guard).  Outside hgr_gemm_plan_capture: a call launches.
+ * hgr_gemm_nt_res_stats_wide_ok is the shape contract (host code, no device needed), 1 exactly when
+ *   M % 320 == 0, N % 256 == 0 (N < 2^20), K % 128 == 0, K >= 256, (M / 320) * (N / 256) <= compute units of the device (256 assumed
+ *   without one), lda, ldw >= K, % 8 == 0 and < 2^21, ldx >= N, % 8 == 0 and < 2^23, M * lda * 2, N * ldw * 2 and M * ldx * 2 below
+ *   2^32 (32-bit byte offsets), dtype HGR_BF16 or HGR_F16;
+ * the entry point rejects everything else (and misaligned or null operands) without launching.
+ */
+int hgr_gemm_nt_res_stats_wide_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldx, int dtype);
+int hgr_gemm_nt_res_stats_wide(const void *A, int64_t lda, const void *W, int64_t ldw, void *xh, void *xl, int64_t ldx,
+                               const float *bias, float *stats, float guard_sumsq, uint32_t *flag,
+                               int M, int N, int K, int dtype, void *stream);
+
+/*
  * Visual head of a ViT in one launch (clip/model.py:231-233: x = ln_post(x[:, 0, :]); x = x @ proj) on the residual stream kept as
  * a pair (above): row b of the result = LayerNorm(decode(xh, xl)[b * row_mul]; gamma, beta, eps) rounded to the MFMA type,
  * times proj_t^T (proj_t [D, W] 16-bit = visual.proj transposed), fp32 [B, D].  row_mul = tokens per image (the class token is

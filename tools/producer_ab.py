@@ -21,6 +21,9 @@ lib.hgr_gemm_nt_res_stats.argtypes = [p, l, p, l, p, p, l, p, p, i, i, i, i, p]
 lib.hgr_gemm_nt_ln.argtypes = [p, l, p, l, p, l, p, p, p, f, i, i, i, i, i, p]
 lib.hgr_last_error.restype = C.c_char_p
 has_tail = hasattr(lib, "hgr_gemm_set_tail")
+has_wide = hasattr(lib, "hgr_gemm_nt_res_stats_wide")           # the 320 x 256 tile producer (csrc/hgr_gemm_wide.hip): arms out_wide / proj_wide
+if has_wide:
+    lib.hgr_gemm_nt_res_stats_wide.argtypes = [p, l, p, l, p, p, l, p, p, f, p, i, i, i, i, p]
 if has_tail:
     lib.hgr_gemm_set_tail.argtypes = [i, i]
 
@@ -56,6 +59,16 @@ def proj(k):
                                   stats.data_ptr(), M, 768, 3072, 1, st()))
 
 
+def out_wide(k):
+    chk(lib.hgr_gemm_nt_res_stats_wide(x768[k % NB].data_ptr(), 768, w_out.data_ptr(), 768, xh[k % NB].data_ptr(), xl[k % NB].data_ptr(), 768, b768.data_ptr(),
+                                       stats.data_ptr(), 0.0, None, M, 768, 768, 1, st()))
+
+
+def proj_wide(k):
+    chk(lib.hgr_gemm_nt_res_stats_wide(u3072[k % NB].data_ptr(), 3072, w_proj.data_ptr(), 3072, xh[k % NB].data_ptr(), xl[k % NB].data_ptr(), 768, b768.data_ptr(),
+                                       stats.data_ptr(), 0.0, None, M, 768, 3072, 1, st()))
+
+
 def qk(k):
     chk(lib.hgr_gemm_nt_ln(x768[k % NB].data_ptr(), 768, w_qkv.data_ptr(), 768, qkv[k & 1].data_ptr(), 2304, s_q.data_ptr(), c_q.data_ptr(), stats.data_ptr(),
                            1e-5, M, 2304, 768, 1, 0, st()))
@@ -82,14 +95,20 @@ if has_tail and os.environ.get("AB_PB"):                      # forced full-pane
     arms += [(f"pb{v}", 1, int(v)) for v in os.environ["AB_PB"].split(",")]
 for _ in range(40):                                           # ~0.2 s of launches first: the first arms otherwise run on ramping clocks
     timeit(fc)
+wide = {"out": out_wide, "proj": proj_wide} if has_wide else {}
 for name, fn in (("out", out), ("proj", proj), ("qkv", qk), ("fc", fc)):
     ts = {tag: [] for tag, _, _ in arms}
+    if name in wide:
+        ts["wide"] = []
     for _ in range(5):                                        # arms interleaved (CDNA guide rule 24)
         for tag, en, pb in arms:
             if en is not None:
                 lib.hgr_gemm_set_tail(en, pb)
             fn(0)
             ts[tag].append(timeit(fn))
+        if name in wide:                                      # the wide entry has no plan: the tail switch does not reach it
+            wide[name](0)
+            ts["wide"].append(timeit(wide[name]))
     for tag, v in ts.items():
         v.sort()
         res[name + ("_" + tag if tag else "")] = [round(v[0], 1), round(v[2], 1)]
