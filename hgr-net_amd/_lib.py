@@ -51,6 +51,11 @@ SIGNATURES = {
     "hgr_avgpool2_nhwc": [_p, _p, _i, _i, _i, _i, _i, _p],
     "hgr_attnpool_tokens": [_p, _p, _p, _i, _i, _i, _i, _p],
     "hgr_attnpool_attend": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "hgr_stem7_pool": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "hgr_stem7_im2col": [_p, _p, _i, _i, _i, _i, _p],
+    "hgr_maxpool3s2_nhwc": [_p, _p, _i, _i, _i, _i, _i, _p],
+    "hgr_subsample2_nhwc": [_p, _p, _i, _i, _i, _i, _i, _p],
+    "hgr_meanpool_nhwc": [_p, _p, _i, _i, _i, _i, _i, _i, _p],
     "hgr_transpose16": [_p, _l, _p, _l, _i, _i, _p],
     "hgr_transpose16_colsum": [_p, _l, _p, _l, _i, _i, _i, _p, _i, _f, _p, _p],
     "hgr_colsum": [_p, _l, _i, _i, _i, _i, _p, _i, _f, _p, _p],

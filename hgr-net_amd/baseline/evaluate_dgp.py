@@ -1,12 +1,16 @@
 """`python -m hgr_net_amd.baseline.evaluate_dgp`: the command line of the reference's baseline/DGP/evaluate_imagenet.py and
 evaluate_21kp.py on the device evaluator (`dgp_eval.DGPEvaluator`).  It reads an `epoch_K.pred` file, scores its classifiers against
-image FEATURES (`--features FILE.npz`, one [n_i, K] array per wnid: tower-free evaluation on cached features), prints the
-reference's per-class lines and its `summary:` line in the reference's formats and writes `{wnid: hits / tot}` to `--output`.
+image FEATURES - cached ones (`--features FILE.npz`, one [n_i, K] array per wnid: tower-free evaluation) or those of images pushed
+through the baseline's ResNet on the device (`--cnn FILE.pth --image-dir DIR`, resnet.ResNetFeatures as the evaluator's `cnn`) -,
+prints the reference's per-class lines and its `summary:` line in the reference's formats and writes `{wnid: hits / tot}` to `--output`.
 
 Reference options: --pred --test-set --output --keep-ratio --consider-trains --graph_path.  Ours: --split_path, --train-set (its
 classes lead the node list and are the seen columns; empty = the 21K-P protocol of evaluate_21kp.py: the test set is the node list,
 n = 0), --features, --batch-size, --dtype, --synthetic N (a generated graph, predictions and features: runs with no material files).
---cnn, --gpu and --test-train are not offered (the reference's --test-train cannot run: wrong call arity, undefined names).
+--cnn FILE.pth is the reference's option (a `make_resnet50_base()` state_dict); it needs --image-dir DIR (one sub-folder per wnid;
+--image-size, --version: extract_features.add_cnn_options, where the unknown transform of the reference is spoken of), or, with
+--synthetic N, `--cnn synthetic` scores generated images through a seeded net end to end.
+--gpu and --test-train are not offered (the reference's --test-train cannot run: wrong call arity, undefined names).
 --keep-ratio keeps the first ceil(ratio * n_i) rows of a class.  The per-class lines are printed after the last batch, from the
 counters read once: no batch waits for the host."""
 from __future__ import annotations
@@ -18,7 +22,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import dgp_eval
+from . import dgp_eval, extract_features
 
 
 def add_eval_options(parser: argparse.ArgumentParser, standalone: bool = True) -> None:
@@ -29,6 +33,7 @@ def add_eval_options(parser: argparse.ArgumentParser, standalone: bool = True) -
         parser.add_argument("--synthetic", type=int, default=None, metavar="N",
                             help="score generated predictions and features on a generated N-node graph instead of the material files")
         parser.add_argument("--seed", type=int, default=0, help="seed of the --synthetic material")
+        extract_features.add_cnn_options(parser)
     parser.add_argument("--test-set", default="rest")
     parser.add_argument("--train-set", default="train", help="split whose classes lead the node list as the seen columns; '' = the 21K-P protocol")
     parser.add_argument("--output", default=None)
@@ -45,6 +50,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     add_eval_options(parser)
     args = parser.parse_args(argv)
     check_args(args)
+    extract_features.check_cnn_args(args, args.synthetic is not None)
+    if args.cnn is not None and args.features is not None:
+        raise SystemExit("--features and --cnn exclude each other: cached features or images")
     return args
 
 
@@ -85,16 +93,23 @@ def synthetic_material(n_nodes: int, seed: int, dim: int = 192):
 
 def evaluate(graph_edges, train_wnids: Sequence[str], test_wnids: Sequence[str], pred, features: Dict[str, np.ndarray],
              consider_trains: bool = False, keep_ratio: float = 1.0, batch_size: int = 256, dtype: str = "f16", device="cuda:0",
-             log=print) -> dict:
+             log=print, cnn=None) -> dict:
     """evaluate_imagenet.py:175-261 on features: every test class with rows is scored in batches of `batch_size`, the class at
-    position i of the test set against column len(train) + i.  Returns `DGPEvaluator.result()` + 'lines' (what was printed)."""
+    position i of the test set against column len(train) + i.  Returns `DGPEvaluator.result()` + 'lines' (what was printed).
+    With `cnn` (images -> features on the device, resnet.ResNetFeatures) `features` holds `extract_features.ImageRows` per wnid."""
     nodes = list(train_wnids) + list(test_wnids)
     log("test set: {} classes, ratio={}".format(len(test_wnids), keep_ratio))
     log("consider train classifiers: {}".format(consider_trains))
-    ev = dgp_eval.DGPEvaluator(graph_edges, nodes, len(train_wnids), pred, consider_trains=consider_trains, dtype=dtype, device=device)
+    ev = dgp_eval.DGPEvaluator(graph_edges, nodes, len(train_wnids), pred, consider_trains=consider_trains, dtype=dtype, device=device,
+                               cnn=cnn)
     for i, wnid in enumerate(test_wnids):
         rows = features.get(wnid)
         if rows is None or len(rows) == 0:                             # evaluate_imagenet.py:235
+            continue
+        if cnn is not None:
+            for o in range(0, dgp_eval.keep_rows(len(rows), keep_ratio), batch_size):
+                n = min(batch_size, dgp_eval.keep_rows(len(rows), keep_ratio) - o)
+                ev.add(rows.batch(o, n, ev.device), len(train_wnids) + i)
             continue
         if rows.shape[1] != ev.k:
             raise ValueError(f"features of '{wnid}' are {rows.shape[1]} wide, the predictions want {ev.k}")
@@ -111,11 +126,12 @@ def evaluate(graph_edges, train_wnids: Sequence[str], test_wnids: Sequence[str],
     return res
 
 
-def run(args: argparse.Namespace, graph_edges, splits: dict, pred, features: Dict[str, np.ndarray], device="cuda:0", log=print) -> dict:
+def run(args: argparse.Namespace, graph_edges, splits: dict, pred, features: Dict[str, np.ndarray], device="cuda:0", log=print,
+        cnn=None) -> dict:
     train = list(splits[args.train_set]) if args.train_set else []
     test = list(splits[args.test_set])
     res = evaluate(graph_edges, train, test, pred, features, consider_trains=args.consider_trains, keep_ratio=args.keep_ratio,
-                   batch_size=args.batch_size, dtype=args.dtype, device=device, log=log)
+                   batch_size=args.batch_size, dtype=args.dtype, device=device, log=log, cnn=cnn)
     if args.output is not None:
         with open(args.output, "w") as f:
             json.dump(res["results"], f)
@@ -126,16 +142,24 @@ def main(argv=None) -> Optional[dict]:
     args = parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("evaluate_dgp needs the GPU: the product path has no CPU fallback")
+    cnn = None
+    if args.cnn is not None:
+        cnn = extract_features.load_cnn(args.cnn, args.version, args.seed)
     if args.synthetic is not None:
-        graph_edges, splits, pred, features = synthetic_material(args.synthetic, args.seed)
+        graph_edges, splits, pred, features = synthetic_material(args.synthetic, args.seed, **({} if cnn is None else {"dim": cnn.out_channels}))
+        if cnn is not None:                                            # generated images instead of generated features
+            features = extract_features.synthetic_rows(splits["rest"], args.seed, args.image_size or extract_features.SYNTHETIC_SIZE)
     else:
-        if args.features is None:
-            raise SystemExit("--features FILE.npz is required (or --synthetic N)")
+        if args.features is None and cnn is None:
+            raise SystemExit("--features FILE.npz or --cnn FILE.pth --image-dir DIR is required (or --synthetic N)")
         graph_edges = json.load(open(args.graph_path, "r"))
         splits = json.load(open(args.split_path, "r"))
         pred = dgp_eval.load_pred(args.pred)
-        features = dgp_eval.load_features(args.features)
-    return run(args, graph_edges, splits, pred, features)
+        if cnn is not None:
+            features = extract_features.image_dir_rows(args.image_dir, args.image_size or 224, "cuda:0", splits[args.test_set])
+        else:
+            features = dgp_eval.load_features(args.features)
+    return run(args, graph_edges, splits, pred, features, cnn=cnn)
 
 
 if __name__ == "__main__":

@@ -904,6 +904,63 @@ def attnpool_attend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torc
     return out
 
 
+# ---- torchvision-style ResNet (baseline/resnet.py) ------------------------------------------------------
+def stem7_geometry(r: int):
+    """(Hc, Hp): conv 7x7 / stride 2 / pad 3 outputs per edge, then max-pool 3x3 / stride 2 / pad 1."""
+    hc = (r - 1) // 2 + 1
+    return hc, (hc - 1) // 2 + 1
+
+
+def _stem7_check(image: torch.Tensor, out: torch.Tensor) -> None:
+    assert image.dtype == torch.float32 and image.is_contiguous() and image.dim() == 4 and image.shape[1] == 3 and image.shape[2] == image.shape[3]
+    assert out.is_contiguous() and out.dtype in DT_OF
+
+
+def stem7_pool(image: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out NHWC [B*Hp*Hp, 64] = maxpool3s2(relu(conv7x7 stride 2 pad 3 (image fp32 NCHW) + bias)) in one launch; w [64, Kp] folded,
+    (ky, kx, c) order."""
+    _stem7_check(image, out)
+    b, r = image.shape[0], image.shape[2]
+    hp = stem7_geometry(r)[1]
+    assert w.is_contiguous() and w.dtype == out.dtype and w.shape[0] == 64 and bias.dtype == torch.float32 and bias.numel() == 64
+    assert out.numel() == b * hp * hp * 64
+    _lib.call("hgr_stem7_pool", _dev(image), _dev(w), _dev(bias), _dev(out), b, r, w.shape[1], DT_OF[out.dtype], _stream())
+    return out
+
+
+def stem7_im2col(image: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out [B*Hc*Hc, Kp] 16-bit: the 147 taps of every conv output in (ky, kx, c) order, zero beyond."""
+    _stem7_check(image, out)
+    b, r = image.shape[0], image.shape[2]
+    hc = stem7_geometry(r)[0]
+    assert out.dim() == 2 and out.shape[0] == b * hc * hc
+    _lib.call("hgr_stem7_im2col", _dev(image), _dev(out), b, r, out.shape[1], DT_OF[out.dtype], _stream())
+    return out
+
+
+def maxpool3s2_nhwc(x: torch.Tensor, out: torch.Tensor, b: int, h: int, w: int, c: int) -> torch.Tensor:
+    assert x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype and x.numel() == b * h * w * c
+    assert out.numel() == b * ((h - 1) // 2 + 1) * ((w - 1) // 2 + 1) * c
+    _lib.call("hgr_maxpool3s2_nhwc", _dev(x), _dev(out), b, h, w, c, DT_OF[x.dtype], _stream())
+    return out
+
+
+def subsample2_nhwc(x: torch.Tensor, out: torch.Tensor, b: int, h: int, w: int, c: int) -> torch.Tensor:
+    """out[b, yo, xo, :] = x[b, 2 yo, 2 xo, :]: the input rows of a 1 x 1 / stride 2 convolution."""
+    assert x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype and x.numel() == b * h * w * c
+    assert out.numel() == b * ((h - 1) // 2 + 1) * ((w - 1) // 2 + 1) * c
+    _lib.call("hgr_subsample2_nhwc", _dev(x), _dev(out), b, h, w, c, DT_OF[x.dtype], _stream())
+    return out
+
+
+def meanpool_nhwc(x: torch.Tensor, out: torch.Tensor, b: int, h: int, w: int, c: int) -> torch.Tensor:
+    """out [b, c] = mean over the h*w cells of x NHWC; out is x's 16-bit type or fp32."""
+    assert x.is_contiguous() and out.is_contiguous() and x.numel() == b * h * w * c and out.numel() == b * c
+    assert out.dtype in (x.dtype, torch.float32)
+    _lib.call("hgr_meanpool_nhwc", _dev(x), _dev(out), b, h, w, c, DT_OF[x.dtype], 1 if out.dtype == torch.float32 else 0, _stream())
+    return out
+
+
 # ---- training: backward / optimizer ------------------------------------------------------------------
 def transpose16(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """out[c, r] = x[r, c]; out is [cols, ld >= rows] (its padding columns must already be zero)."""

@@ -16,6 +16,7 @@ parity tests would exercise nothing) and LayerNorm/BatchNorm affine terms are pe
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Dict, List, Sequence, Tuple
 
@@ -215,6 +216,44 @@ def clip_state_dict(config: str | dict, seed: int = 0) -> Dict[str, torch.Tensor
     # so "same weights" means the same bits on both sides.
     for k, v in sd.items():
         if v.dtype == torch.float32 and k != "logit_scale":
+            sd[k] = v.to(torch.float16).to(torch.float32)
+    return sd
+
+
+RESNET_LAYERS = {"resnet50": (3, 4, 6, 3), "resnet101": (3, 4, 23, 3), "resnet152": (3, 8, 36, 3)}
+
+
+def resnet_state_dict(version: str = "resnet50", seed: int = 0) -> Dict[str, torch.Tensor]:
+    """fp32 state_dict of the DGP baseline's torchvision-style ResNet base (reference baseline/DGP/models/resnet.py:97-137), keys in the
+    module's own order.  As in clip_state_dict: He-scaled convolutions, perturbed BatchNorm terms, gain 0.25 on every bn3 (keeps the 16
+    residual adds O(1)) and fp16-representable values.  25 M hashed normals take seconds: the last few results are kept, and every
+    call gets tensors of its own."""
+    return {k: v.clone() for k, v in _resnet_state_dict(version, seed).items()}
+
+
+@functools.lru_cache(maxsize=2)
+def _resnet_state_dict(version: str, seed: int) -> Dict[str, torch.Tensor]:
+    sd: Dict[str, torch.Tensor] = {}
+    _conv(sd, seed, "conv1.weight", 64, 3, 7)
+    _bn(sd, seed, "bn1", 64)
+    inplanes = 64
+    for li, nblocks in enumerate(RESNET_LAYERS[version]):
+        planes = 64 * (2 ** li)
+        stride = 1 if li == 0 else 2
+        for j in range(nblocks):
+            p = f"layer{li + 1}.{j}"
+            _conv(sd, seed, p + ".conv1.weight", planes, inplanes, 1)
+            _bn(sd, seed, p + ".bn1", planes)
+            _conv(sd, seed, p + ".conv2.weight", planes, planes, 3)
+            _bn(sd, seed, p + ".bn2", planes)
+            _conv(sd, seed, p + ".conv3.weight", planes * 4, planes, 1)
+            _bn(sd, seed, p + ".bn3", planes * 4, gain=0.25)
+            if j == 0 and (stride > 1 or inplanes != planes * 4):
+                _conv(sd, seed, p + ".downsample.0.weight", planes * 4, inplanes, 1)
+                _bn(sd, seed, p + ".downsample.1", planes * 4)
+            inplanes = planes * 4
+    for k, v in sd.items():
+        if v.dtype == torch.float32:
             sd[k] = v.to(torch.float16).to(torch.float32)
     return sd
 

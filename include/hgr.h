@@ -491,6 +491,28 @@ int hgr_attnpool_tokens(const void *x, const float *pos, void *out, int B, int S
 int hgr_attnpool_attend(const float *q, const void *k, const void *v, void *out, int B, int L, int heads,
                         int dtype, void *stream);
 
+/*
+ * ---- torchvision-style ResNet (baseline/DGP/models/resnet.py: the DGP baseline's feature extractor; csrc/hgr_resnet_tv.hip) ----
+ * Stem geometry: Hc = (R - 1) / 2 + 1 conv outputs per edge (7 x 7, stride 2, pad 3), Hp = (Hc - 1) / 2 + 1 pooled (3 x 3, stride 2,
+ * pad 1).  w is the folded conv1 weight, 16-bit [64, Kp] in (ky, kx, c) order, zero beyond column 147; bias fp32 [64].
+ * Rounding contract of both routes: relu(conv + bias) is rounded to 16 bit once, the max is taken over those 16-bit values; a pool
+ * tap outside the map is ignored.
+ */
+/* The fused stem: out NHWC 16-bit [B, Hp, Hp, 64] = maxpool(relu(conv7x7(image fp32 [B, 3, R, R]) + bias)); the [B, Hc, Hc, 64]
+ * tensor is never written.  Any R >= 1. */
+int hgr_stem7_pool(const float *image, const void *w, const float *bias, void *out, int B, int R, int Kp, int dtype, void *stream);
+/* The unfused route's im2col: out 16-bit [B*Hc*Hc, Kp] (Kp a multiple of 8, >= 152), followed by hgr_gemm_nt with HGR_EPI_BIAS_RELU
+ * and hgr_maxpool3s2_nhwc. */
+int hgr_stem7_im2col(const float *image, void *out, int B, int R, int Kp, int dtype, void *stream);
+/* nn.MaxPool2d(3, stride 2, padding 1), NHWC 16-bit [B, H, W, C] -> [B, (H-1)/2+1, (W-1)/2+1, C]; C % 8 == 0, any H, W >= 1. */
+int hgr_maxpool3s2_nhwc(const void *x, void *out, int B, int H, int W, int C, int dtype, void *stream);
+/* out[b, yo, xo, :] = x[b, 2 yo, 2 xo, :] (NHWC 16-bit, C % 8 == 0): the rows a 1 x 1 / stride 2 convolution reads, i.e. the A
+ * operand of the hgr_gemm_nt that is the `downsample` branch of the first block of layers 2 - 4. */
+int hgr_subsample2_nhwc(const void *x, void *out, int B, int H, int W, int C, int dtype, void *stream);
+/* Global mean (resnet.py:150): out[b, c] = (sum over the H W cells, fp32, in cell order) / (H W), one true division; out is the
+ * 16-bit type of x (rounded once) or, with out_f32 = 1, fp32.  C % 8 == 0. */
+int hgr_meanpool_nhwc(const void *x, void *out, int B, int H, int W, int C, int dtype, int out_f32, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * OM training step (model/clip_tree.py:222-281 `train_batch`, main.py:86-94): backward + optimizer.
  * GEMM gradients reuse hgr_gemm_nt: dX = dY . W is an NT product against the pre-transposed weight,
