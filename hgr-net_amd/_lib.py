@@ -137,6 +137,12 @@ SIGNATURES = {
     "hgr_allgather": [_p, _p, _l, _i, _p],
     "hgr_broadcast": [_p, _l, _i, _i, _p],
     "hgr_adamw": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _f, _f, _p],
+    "hgr_normal_counter": [_p, _l, _p, _i, _i, _i, _i, _l, _p],
+    "hgr_free_gen_input": [_p, _l, _i, _p, _l, _p, _l, _i, _p, _i, _i, _i, _i, _i, _i, _i, _l, _p],
+    "hgr_bias_act_rows": [_p, _l, _p, _p, _l, _l, _i, _i, _i, _i, _p],
+    "hgr_free_fr_tail": [_p, _l, _p, _p, _l, _p, _l, _l, _i, _p, _l, _i, _i, _i, _i, _l, _p],
+    "hgr_nll_rows16": [_p, _l, _p, _i, _i, _p, _p, _l, _p, _l, _i, _p],
+    "hgr_adam_l2_cast16": [_p, _p, _l, _i, _f, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _i, _p],
 }
 
 

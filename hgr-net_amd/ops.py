@@ -1363,3 +1363,93 @@ def adamw(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr
     assert p.is_contiguous() and g.is_contiguous() and p.dtype == g.dtype == m.dtype == v.dtype == torch.float32
     WEIGHTS_GEN[0] += 1
     _lib.call("hgr_adamw", _dev(p), _dev(g), _dev(m), _dev(v), p.numel(), lr, betas[0], betas[1], eps, wd, step, _dev(sumsq_total), max_norm, grad_scale, _stream())
+
+
+# ---- FREE baseline (baseline/free.py) ------------------------------------------------------------------------------------------------------
+OUT_F32 = 2                         # HGR_OUT_F32: the fp32 value of an `out_type`
+ACT_LRELU02, ACT_SIGMOID = 0, 1     # HGR_ACT_*
+NLL_RESIDENT_COLS = 18432           # HGR_NLL_RESIDENT_COLS: up to this many columns hgr_nll_rows16 keeps a row in LDS
+
+
+def _out_type(t: torch.Tensor) -> int:
+    if t.dtype == torch.float32:
+        return OUT_F32
+    if t.dtype not in DT_OF:
+        raise _lib.HgrError(f"destination must be bf16, f16 or fp32, got {t.dtype}")
+    return DT_OF[t.dtype]
+
+
+def _seed32(seed: int) -> int:
+    seed &= 0xFFFFFFFF
+    return seed - (1 << 32) if seed >> 31 else seed
+
+
+def normal_counter(out: torch.Tensor, seed: int, stream: int, row0: int = 0, bits: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r, c] = baseline.free.normal_host(seed, stream, row0 + r, c): counter-based N(0, 1), fp32.  `bits` (int32 [rows, C, 2],
+    optional) receives the two 32-bit draws of every element."""
+    assert _f32_rows(out) and (bits is None or (bits.dtype == torch.int32 and bits.is_contiguous() and bits.numel() == 2 * out.numel()))
+    _lib.call("hgr_normal_counter", _dev(out), out.stride(0), _dev(bits), out.shape[0], out.shape[1], _seed32(seed), stream, row0, _stream())
+    return out
+
+
+def free_gen_input(out: torch.Tensor, attribute: torch.Tensor, classes: torch.Tensor, num: int, nz: int, seed: int = 0, stream: int = 0,
+                   row0: int = 0, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [rows, nz + A] = cat(noise, attribute[classes[(row0 + r) // num]]) for the synthetic rows [row0, row0 + rows): the noise
+    is the counter normal of (seed, stream, row0 + r, c), or `z` [rows, nz] fp32."""
+    assert out.dim() == 2 and out.stride(1) == 1 and _f32_rows(attribute) and classes.dtype == torch.int32 and classes.is_contiguous()
+    assert z is None or (_f32_rows(z) and z.shape == (out.shape[0], nz))
+    a = attribute.shape[1]
+    assert out.shape[1] == nz + a
+    _lib.call("hgr_free_gen_input", _dev(out), out.stride(0), _out_type(out), _dev(z), z.stride(0) if z is not None else 0, _dev(attribute),
+              attribute.stride(0), attribute.shape[0], _dev(classes), classes.numel(), num, out.shape[0], nz, a, _seed32(seed), stream, row0, _stream())
+    return out
+
+
+def bias_act_rows(x: torch.Tensor, bias: torch.Tensor, y: torch.Tensor, act: int, col0: int = 0) -> torch.Tensor:
+    """y[:, col0:col0 + C] = act(x + bias): act = ACT_LRELU02 or ACT_SIGMOID; y bf16 / f16 / fp32, the rest of y untouched."""
+    assert _f32_rows(x) and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == x.shape[0] and y.shape[1] >= col0 + x.shape[1]
+    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == x.shape[1]
+    _lib.call("hgr_bias_act_rows", _dev(x), x.stride(0), _dev(bias), _dev(y), y.stride(0), col0, _out_type(y), act, x.shape[0], x.shape[1], _stream())
+    return y
+
+
+def free_fr_tail(lantent: torch.Tensor, y: torch.Tensor, col0: int = 0, bias: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
+                 seed: int = 0, stream: int = 0, row0: int = 0, mus: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[:, col0:col0 + A] = sigmoid(mu + eps * sigmoid(sd)), (mu, sd) = the halves of lantent [rows, 2A] (+ bias); `eps` [rows, A]
+    fp32 or the counter normals of (seed, stream, row0 + r, c); `mus` [rows, A] fp32 receives mu."""
+    assert _f32_rows(lantent) and lantent.shape[1] % 2 == 0 and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == lantent.shape[0]
+    rows, a = lantent.shape[0], lantent.shape[1] // 2
+    assert y.shape[1] >= col0 + a and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == 2 * a))
+    assert (eps is None or (_f32_rows(eps) and eps.shape == (rows, a))) and (mus is None or (_f32_rows(mus) and mus.shape == (rows, a)))
+    _lib.call("hgr_free_fr_tail", _dev(lantent), lantent.stride(0), _dev(bias), _dev(eps), eps.stride(0) if eps is not None else 0, _dev(y),
+              y.stride(0), col0, _out_type(y), _dev(mus), mus.stride(0) if mus is not None else 0, rows, a, _seed32(seed), stream, row0, _stream())
+    return y
+
+
+def nll_rows16(logits: torch.Tensor, labels: Optional[torch.Tensor], n: Optional[int] = None, loss_rows: Optional[torch.Tensor] = None,
+               dlogits: Optional[torch.Tensor] = None, logsm: Optional[torch.Tensor] = None, dtype=None) -> None:
+    """NLLLoss(LogSoftmax) over the first `n` columns of fp32 logits [rows, ld]: loss_rows [rows]; dlogits 16-bit [rows, >= ld] =
+    softmax - onehot (unscaled, columns [n, ld) zero); logsm fp32 (may be `logits`) = the log-softmax of columns [0, n)."""
+    assert _f32_rows(logits) and (labels is None or (labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == logits.shape[0]))
+    rows, ld = logits.shape[0], logits.stride(0)
+    n = logits.shape[1] if n is None else n
+    assert 1 <= n <= logits.shape[1]
+    assert loss_rows is None or (loss_rows.dtype == torch.float32 and loss_rows.is_contiguous() and loss_rows.numel() == rows)
+    assert dlogits is None or (dlogits.dtype in DT_OF and dlogits.dim() == 2 and dlogits.stride(1) == 1 and dlogits.shape[0] == rows and dlogits.shape[1] >= ld)
+    assert logsm is None or (_f32_rows(logsm) and logsm.shape[0] == rows and logsm.shape[1] >= n)
+    dt = DT_OF[dlogits.dtype] if dlogits is not None else (HGR_BF16 if dtype is None else dtype_code(dtype))
+    _lib.call("hgr_nll_rows16", _dev(logits), ld, _dev(labels), rows, n, _dev(loss_rows), _dev(dlogits), dlogits.stride(0) if dlogits is not None else 0,
+              _dev(logsm), logsm.stride(0) if logsm is not None else 0, dt, _stream())
+
+
+def adam_l2_cast16(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, w16: torch.Tensor, lr: float, step: int, slices: int = 1,
+                   alpha: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8, wd: float = 0.0) -> None:
+    """`adam_l2` on g' = alpha * (g[0] + ... + g[slices - 1]) (g: `slices` contiguous slices of p.numel() floats, added in order),
+    and w16 = (16-bit) p, in one pass over the weight."""
+    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous() and w16.is_contiguous()
+    assert p.dtype == g.dtype == m.dtype == v.dtype == torch.float32 and w16.dtype in DT_OF
+    n = p.numel()
+    assert m.numel() == v.numel() == w16.numel() == n and g.numel() >= slices * n and slices >= 1
+    WEIGHTS_GEN[0] += 1
+    _lib.call("hgr_adam_l2_cast16", _dev(p), _dev(g), n, slices, alpha, _dev(m), _dev(v), _dev(w16), n, lr, betas[0], betas[1], eps, wd, step,
+              DT_OF[w16.dtype], _stream())

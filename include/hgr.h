@@ -984,6 +984,81 @@ int hgr_allreduce(const void *send, void *recv, int64_t count, int dtype, int op
 int hgr_allgather(const void *send, void *recv, int64_t count_per_rank, int dtype, void *stream);
 int hgr_broadcast(void *buf, int64_t count, int dtype, int root, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FREE baseline, validation route (baseline/FREE/validate.py, classifier.py, model.py): feature synthesis, the softmax
+ * classifier on cat(x, hidden, h) and its scoring.  The products are hgr_gemm_nt / hgr_gemm_tn_splitk / hgr_matmul_f32; these
+ * are the row kernels between them.  `out_type`: HGR_BF16, HGR_F16 or HGR_OUT_F32.  A 16-bit value is ONE rounding of the fp32
+ * value; sums run in a fixed order; no atomics: a repeated launch writes the same bits.
+ * ------------------------------------------------------------------------------------------------ */
+#define HGR_OUT_F32 2
+#define HGR_ACT_LRELU02 0
+#define HGR_ACT_SIGMOID 1
+#define HGR_NLL_RESIDENT_COLS 18432
+
+/*
+ * Counter-based standard normal: z[r, c] for r < rows, c < C is a function of (seed, stream_id, row0 + r, c) only - not of the
+ * launch, of ld_z or of how the rows are split into calls.  With fmix32 = murmur3's 32-bit finaliser and 32-bit wrap-around arithmetic,
+ *     key = fmix32(fmix32(seed + 0x9E3779B9 * (stream_id + 1)) ^ 0xC2B2AE35)
+ *     rk  = fmix32(fmix32(key ^ low32(row)) + 0x9E3779B9 * (high32(row) + 1))
+ *     a   = fmix32(rk ^ (2 c)),   b = fmix32(rk ^ (2 c + 1))
+ *     z   = sqrt(-2 ln(((a >> 9) + 1/2) 2^-23)) * cos(pi (b >> 8) 2^-23)                    (Box-Muller, library logf / cospif)
+ * The row is a 64-bit number (1.3 M rows x 1024 columns is close to 2^32 elements).  Not torch's generator: only the distribution is
+ * the goal (syn_noise.normal_(0, 1) of classifier.py:34, torch.randn_like of model.py:131).  bits (optional) uint32 [rows, C, 2]
+ * receives (a, b).  C % 4 == 0.  This entry exists for tests; hgr_free_gen_input and hgr_free_fr_tail draw the same numbers.
+ */
+int hgr_normal_counter(float *z, int64_t ld_z, uint32_t *bits, int rows, int C, int seed, int stream_id, int64_t row0, void *stream);
+
+/*
+ * The generator's input torch.cat((z, c), -1) of generate_syn_feature (classifier.py:21-43, model.py:58) for the global synthetic
+ * rows [row0, row0 + rows): out [rows, nz + A] (`out_type`), columns [0, nz) the counter normals of row row0 + r (or z [rows, ld_z]
+ * fp32 when z is given), columns [nz, nz + A) row classes[(row0 + r) / num] of att [att_rows, ld_att] fp32.  classes int32
+ * [n_classes]; a class outside the table gives NaN.  nz, A multiples of 8; row0 + rows <= n_classes * num.
+ */
+int hgr_free_gen_input(void *out, int64_t ld_out, int out_type, const float *z, int64_t ld_z, const float *att, int64_t ld_att,
+                       int att_rows, const int32_t *classes, int n_classes, int num, int rows, int nz, int A, int seed,
+                       int stream_id, int64_t row0, void *stream);
+
+/*
+ * y[r, col0 + c] = act(x[r, c] + bias[c]) for fp32 x [rows, ld_x]: act = HGR_ACT_LRELU02 (nn.LeakyReLU(0.2), model.py:59,109) or
+ * HGR_ACT_SIGMOID (model.py:60).  y is `out_type` with its own leading dimension and column offset, so that it can land inside the
+ * concatenated classifier input (classifier.py:332).  C, col0, ld_y multiples of 8; ld_x a multiple of 4.
+ */
+int hgr_bias_act_rows(const float *x, int64_t ld_x, const float *bias, void *y, int64_t ld_y, int64_t col0, int out_type, int act,
+                      int rows, int C, void *stream);
+
+/*
+ * The tail of FR.forward (model.py:110-121): with (mu, sd) = the two halves of lantent [rows, 2A] fp32 (+ bias [2A], optional),
+ * y[r, col0 + c] = sigmoid(mu + eps * sigmoid(sd)), eps [rows, ld_eps] fp32 or, when eps is NULL, the counter normals of
+ * (seed, stream_id, row0 + r, c).  mus (optional, fp32 [rows, ld_mus]) receives mu.  A, col0, ld_y multiples of 8.
+ */
+int hgr_free_fr_tail(const float *lantent, int64_t ld_l, const float *bias, const float *eps, int64_t ld_eps, void *y, int64_t ld_y,
+                     int64_t col0, int out_type, float *mus, int64_t ld_mus, int rows, int A, int seed, int stream_id, int64_t row0,
+                     void *stream);
+
+/*
+ * nn.NLLLoss on nn.LogSoftmax (classifier.py:81,369) over fp32 logits [rows, ld] with n <= ld valid columns; any of
+ *     loss_rows[r]  = lse(logits[r]) - logits[r, labels[r]]                     (NaN for a label outside [0, n))
+ *     dlogits [rows, ld_d] 16-bit (`dtype`) = softmax - onehot, UNSCALED (the 1 / rows belongs to the gradient reduction: in f16
+ *                     (1 / 18278) / 1512 is below the smallest subnormal); columns [n, ld) are written as zeros
+ *     logsm [rows, ld_ls] fp32 = logits - lse on columns [0, n); may be `logits` itself
+ * One workgroup per row.  Up to HGR_NLL_RESIDENT_COLS columns the row is read from memory once and stays in LDS between the
+ * max / sum passes and the write pass; beyond, a running (max, sum) pass and the write pass read it twice.
+ * ld, ld_d multiples of 8, ld_d >= ld; ld_ls a multiple of 4; rows, n >= 1.
+ */
+int hgr_nll_rows16(const float *logits, int64_t ld, const int32_t *labels, int rows, int n, float *loss_rows, void *dlogits,
+                   int64_t ld_d, float *logsm, int64_t ld_ls, int dtype, void *stream);
+
+/*
+ * The optimiser step of a large fp32 master weight with its gradient reduction and its 16-bit operand refresh in one pass:
+ *     g' = alpha * (g[0] + g[1] + ... + g[n_slices - 1])      slices `slice_stride` elements apart (the partials of
+ *                                                             hgr_gemm_tn_splitk), added in that order in fp32
+ *     p, m, v <- hgr_adam_l2's update with g'                 (the same bits as that entry fed g')
+ *     w16 = (16-bit) p
+ * n % 4 == 0.
+ */
+int hgr_adam_l2_cast16(float *p, const float *g, int64_t slice_stride, int n_slices, float alpha, float *m, float *v, void *w16,
+                       int64_t n, float lr, float beta1, float beta2, float eps, float wd, int step, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
