@@ -26,7 +26,6 @@ SIGNATURES = {
     "hgr_gemm_set_tile": [_i],
     "hgr_gemm_set_tail": [_i, _i],
     "hgr_gemm_set_persist": [_i],
-    "hgr_gemm_set_ws": [_i],
     "hgr_gemm_set_p8": [_i],
     "hgr_im2col_patches": [_p, _p, _i, _i, _i, _i, _i, _p],
     "hgr_im2col_patches_ex": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p],

@@ -11,7 +11,7 @@
 
 #define HGR_WAVE 64
 
-// Ablation switches (HGR_GEMM_DBG, HGR_WS_DBG, HGR_LS_DBG, HGR_LE_DBG: parts of a kernel left out for timing experiments - WRONG
+// Ablation switches (HGR_GEMM_DBG, HGR_LS_DBG, HGR_LE_DBG: parts of a kernel left out for timing experiments - WRONG
 // results) exist in `make lab` builds only (-DHGR_LAB, ../lib/libhgr_lab.so).  In libhgr.so HGR_LAB_ON() is the constant false: the
 // branches fold away and no environment variable can switch a product kernel into a wrong-result mode.
 #ifdef HGR_LAB
@@ -142,12 +142,8 @@ template <int DT> __device__ __forceinline__ unsigned pair_split2(float x0, floa
     if (DT == HGR_F16) {
         typedef __attribute__((ext_vector_type(2))) _Float16 h2;
         h2 h;
-#if defined(HGR_PAIR_RTZ) && HGR_PAIR_RTZ       // experiment: truncating conversion of t instead of mask + exact conversion (differs below the f16 normal range only)
-        h = __builtin_bit_cast(h2, __builtin_amdgcn_cvt_pkrtz(__uint_as_float(t0), __uint_as_float(t1)));
-#else
         h[0] = (_Float16)__uint_as_float(t0 & ~((1u << S) - 1u));
         h[1] = (_Float16)__uint_as_float(t1 & ~((1u << S) - 1u));
-#endif
         tq0 = __builtin_fabsf(__uint_as_float(t0)) < 6.103515625e-05f ? (128u << (S - 8)) : t0;
         tq1 = __builtin_fabsf(__uint_as_float(t1)) < 6.103515625e-05f ? (128u << (S - 8)) : t1;
         return __builtin_bit_cast(unsigned, h);

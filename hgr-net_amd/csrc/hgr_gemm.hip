@@ -1,4 +1,4 @@
-// Host entry points of the NT GEMM family (kernels: hgr_gemm_128 / _256 / _duo / _ws / _p8 .hip, hgr_conv_direct.hip).  Every entry point is
+// Host entry points of the NT GEMM family (kernels: hgr_gemm_128 / _256 / _duo / _p8 .hip, hgr_conv_direct.hip).  Every entry point is
 // validate -> plan -> launch: the plan functions below are plain host code that decide kernel, tile plan and grid (GemmLaunch) and launch
 // nothing; gemm_run() hands a plan to the launchers, which only select a template instantiation - or, when hgr_gemm_plan_capture armed
 // the calling thread, writes it out instead (tests/golden/gemm_plans.json pins the plan of every route on a machine without a GPU).
@@ -13,7 +13,7 @@ namespace {
 constexpr int BM = 128, BN = 128;
 
 // ---- development knobs (HgrKnob, hgr_common.h: the environment gives the initial value, the hgr_gemm_set_* setters win from then on) ----
-HgrKnob<> k_group{"HGR_GEMM_GROUP", 0, [](int v) { return v < 0 ? 0 : v; }};      // raster group of gemm_nt_duo / _ws; 0 = by shape (duo_group_for)
+HgrKnob<> k_group{"HGR_GEMM_GROUP", 0, [](int v) { return v < 0 ? 0 : v; }};      // raster group of gemm_nt_duo; 0 = by shape (duo_group_for)
 HgrKnob<> k_tail{"HGR_DUO_TAIL", 1}, k_pb{"HGR_DUO_PB", -1};                       // hgr_gemm_set_tail: tail plan on / off, forced full panels
 HgrKnob<double> k_half_cost{"HGR_DUO_HALF_COST", 0.55, [](double v) { return v > 0.1 ? v : 0.55; }};
 HgrKnob<> k_tile{"HGR_GEMM_TILE", 0};                                              // hgr_gemm_set_tile: 0 | 128 | 256 | 2
@@ -24,12 +24,9 @@ HgrKnob<> k_conv_direct{"HGR_CONV_DIRECT", 1}, k_conv_duo{"HGR_CONV_DUO", 1};   
 // launch persistent 5.064 -> 5.008 ms (-1.1 %; by shape proj 128.6 -> 123.5 us, out 50.1 -> 48.5, fc unchanged), the producers only
 // 5.137 -> 5.104 (-0.6 %).  Bit-identical.
 HgrKnob<> k_persist{"HGR_DUO_PERSIST", 1, hgr_knob_bool};                          // hgr_gemm_set_persist
-// gemm_nt_ws, default OFF: measured equal to or slower than gemm_nt_duo on every tower shape (profiles/NOTES.md, round 5) - the epilogue's
-// vector instructions cost their SIMD's matrix wave the same issue slots whichever wave executes them, and LDS bandwidth bounds both
-HgrKnob<> k_ws{"HGR_WS", 0, hgr_knob_bool};                                        // hgr_gemm_set_ws
 HgrKnob<> k_p8{"HGR_P8", 2, [](int v) { return v >= 0 && v <= 2 ? v : 2; }};       // hgr_gemm_set_p8: 0 never, 1 wherever p8_covers, 2 by shape (p8_wanted)
 
-int duo_group() { return k_group.get() ? k_group.get() : 4; }          // gemm_nt_ws, and m-fastest rasters of gemm_nt_duo
+int duo_group() { return k_group.get() ? k_group.get() : 4; }          // m-fastest rasters of gemm_nt_duo, and the group field of a gemm_nt_p8 plan
 // Row panels per raster group of a gemm_nt_duo launch (plan_duo).  By shape unless HGR_GEMM_GROUP=n forces n: 4 (64 tiles in flight per
 // XCD = 4 row panels x 16 column panels), but ONE for launches of at most 8 column panels - the few tiles that share an activation
 // panel are then dispatched back to back instead of 4 slots apart.  Measured (tools/raster_split_ab.sh, FETCH_SIZE per launch, ViT-B/32
@@ -46,9 +43,9 @@ int duo_dbg() {
 // call it covers (hgr_gemm_nt's split plan makes two launches over disjoint row ranges)
 struct GemmLaunch {
     int kernel = 0;               // HGR_KERNEL_* (hgr.h); 0 = no launch
-    int variant = 0;              // V128_* | conv of gemm_nt_256 | ln form of gemm_nt_duo | WS_* | input channels of the direct convolution
+    int variant = 0;              // V128_* | conv of gemm_nt_256 | ln form of gemm_nt_duo | input channels of the direct convolution
     int epilogue = HGR_EPI_NONE; bool out32 = false;
-    int act = 0;                  // gemm_nt_ws / gemm_nt_p8: 0 none, 1 QuickGELU, 2 ReLU
+    int act = 0;                  // gemm_nt_p8: 0 none, 1 QuickGELU
     unsigned grid_x = 0, grid_y = 1;
     int tiles_m = 0, tiles_n = 0, total = 0, nbig = 0, big_panels = 0, tiles_m_half = 0, group = 0;      // -> GemmArgs
     int row0 = 0, rows = 0;
@@ -148,15 +145,6 @@ GemmLaunch plan_duo(const GemmArgs &a, int ln, int epi, bool out32) {
     return L;
 }
 
-// gemm_nt_ws: whole 256 x 128 tiles (ws_covers), one persistent workgroup per CU walks them
-GemmLaunch plan_ws(int M, int N, int mode, int epi, int act) {
-    GemmLaunch L;
-    L.kernel = HGR_KERNEL_WS; L.variant = mode; L.epilogue = epi; L.out32 = mode == WS_LNP; L.act = act; L.rows = M;
-    L.tiles_m = M / 256; L.tiles_n = N / 128; L.total = L.tiles_m * L.tiles_n; L.group = duo_group();
-    L.grid_x = (unsigned)(ws_cus() < L.total ? ws_cus() : L.total);
-    return L;
-}
-
 // gemm_nt_p8: whole 256 x 256 tiles (p8_covers), one persistent workgroup per CU walks them
 GemmLaunch plan_p8(int M, int N, int act) {
     GemmLaunch L;
@@ -212,7 +200,6 @@ int gemm_run(const char *who, const GemmArgs &call, const GemmLaunch *plan, int 
             case HGR_KERNEL_128: launch_128(a, dtype, L.epilogue, L.out32, L.variant, grid, s); break;
             case HGR_KERNEL_256: launch_256(a, dtype, L.epilogue, L.out32, L.variant != 0, grid, s); break;
             case HGR_KERNEL_DUO: launch_duo(a, dtype, L.epilogue, L.out32, L.variant, grid, s); break;
-            case HGR_KERNEL_WS: launch_ws(a, dtype, L.variant, L.act, L.variant != WS_LNC && epi_has_bias(L.epilogue), grid, s); break;   // hasb selects among the WS_PLAIN instantiations only
             default: launch_p8(a, dtype, L.act, grid, s); break;
         }
     }
@@ -245,11 +232,6 @@ extern "C" int hgr_gemm_set_tile(int tile) {
     return k_tile.set(tile);
 }
 
-extern "C" int hgr_gemm_set_ws(int enabled) {
-    HGR_REQUIRE(enabled == 0 || enabled == 1, "hgr_gemm_set_ws: enabled must be 0 or 1, got %d", enabled);
-    return k_ws.set(enabled);
-}
-
 extern "C" int hgr_gemm_set_p8(int mode) {
     HGR_REQUIRE(mode >= 0 && mode <= 2, "hgr_gemm_set_p8: mode must be 0 (never), 1 (wherever it covers) or 2 (by shape), got %d", mode);
     return k_p8.set(mode);
@@ -263,7 +245,7 @@ extern "C" int hgr_gemm_set_persist(int enabled) {
 // ---- hgr_gemm_nt ---------------------------------------------------------------------------------------------------------
 namespace {
 // Kernel and tile plan of one hgr_gemm_nt call (validated; `a` = the whole call): one launch, or two for the split plan.  Returns the count.
-int plan_gemm_nt(const GemmArgs &a, int epilogue, bool out_f32, bool ws_operands_ok, GemmLaunch plan[2]) {
+int plan_gemm_nt(const GemmArgs &a, int epilogue, bool out_f32, GemmLaunch plan[2]) {
     const int M = a.M, N = a.N, K = a.K;
     // rows [m_lo, m_lo + m_cnt) with one tile size
     auto tiled = [&](int m_lo, int m_cnt, bool big) {
@@ -307,13 +289,7 @@ int plan_gemm_nt(const GemmArgs &a, int epilogue, bool out_f32, bool ws_operands
     // ... and an output much narrower than its 128-column tiles (the 64-channel ResNet stage: half of every tile would be padding;
     // measured 252 vs 194 us on the 256 x 64 arrangement of the small kernel) stays where it was
     const bool duo_fits = (N + 127) / 128 * 128 - N <= N / 8;
-    // the role-split kernel (gemm_nt_ws: the epilogue runs in helper waves under the next tile's MFMAs) for 16-bit outputs made of whole tiles
-    // (not BIAS_QUICKGELU: in gemm_nt_duo's plain f16 instantiation hipcc fuses the last product of QuickGELU with the conversion -
-    // v_fma_mixlo_f16, ONE rounding - and does not in the row-layout epilogue; the folded-LayerNorm form, the one the towers use, matches)
-    const bool ws_epi = epilogue == HGR_EPI_NONE || epilogue == HGR_EPI_BIAS || epilogue == HGR_EPI_BIAS_RELU;
-    if (duo_ok && force == 0 && k_ws.get() && !out_f32 && ws_epi && ws_operands_ok && ws_covers(M, N, K, WS_PLAIN))
-        plan[0] = plan_ws(M, N, WS_PLAIN, epilogue, epilogue == HGR_EPI_BIAS_RELU ? 2 : 0);
-    else if (duo_ok && (force == 2 || (force == 0 && tduo >= 256 && duo_fits))) plan[0] = plan_duo(a, 0, epilogue, out_f32);
+    if (duo_ok && (force == 2 || (force == 0 && tduo >= 256 && duo_fits))) plan[0] = plan_duo(a, 0, epilogue, out_f32);
     else if (force == 128 || K < 128) plan[0] = tiled(0, M, false);
     else if (epi_has_idn16(epilogue) && force != 256) plan[0] = tiled(0, M, false);   // only the 128 kernel loads the identity / stores by full lines
     else if (force == 256) plan[0] = tiled(0, M, true);
@@ -347,10 +323,8 @@ extern "C" int hgr_gemm_nt(const void *A, int64_t lda, const void *W, int64_t ld
     if (epi_has_idn16(epilogue)) vec = vec && (ldr % 4 == 0) && hgr_aligned(residual, 8);
     GemmArgs a = gemm_args(A, lda, W, ldw, C, ldc, M, N, K, vec, duo_dbg());
     a.bias = bias; a.res = (const float *)residual; a.ldr = ldr;
-    const bool ws_operands_ok = ldc % 8 == 0 && ldc < (1 << 23) && hgr_aligned(C, 16) && (!bias || hgr_aligned(bias, 16));
     GemmLaunch plan[2];
-    const int n = plan_gemm_nt(a, epilogue, out_f32 != 0, ws_operands_ok, plan);
-    if (plan[0].kernel == HGR_KERNEL_WS) { a.res = nullptr; a.ldr = 0; a.vec_ok = 1; }     // its three epilogues have no second operand
+    const int n = plan_gemm_nt(a, epilogue, out_f32 != 0, plan);
     return gemm_run("hgr_gemm_nt", a, plan, n, dtype, stream);
 }
 
@@ -475,8 +449,7 @@ extern "C" int hgr_gemm_nt_res_stats_guard(const void *A, int64_t lda, const voi
     a.bias = bias;
     a.ln_stats = stats; a.ln_slots = N / 64; a.ln_xh = xh; a.ln_xl = xl; a.ln_ldx = ldx;
     a.ln_flag = flag; a.ln_guard = guard_sumsq;
-    const GemmLaunch L = k_ws.get() && k_tile.get() == 0 && ws_covers(M, N, K, WS_LNP) ? plan_ws(M, N, WS_LNP, HGR_EPI_BIAS_RESIDUAL, 0)
-                                                                                        : plan_duo(a, 1, HGR_EPI_BIAS_RESIDUAL, true);
+    const GemmLaunch L = plan_duo(a, 1, HGR_EPI_BIAS_RESIDUAL, true);
     return gemm_run("hgr_gemm_nt_res_stats", a, &L, 1, dtype, stream);
 }
 
@@ -494,9 +467,7 @@ extern "C" int hgr_gemm_nt_ln(const void *X16, int64_t ldx, const void *Wfold, i
     GemmArgs a = gemm_args(X16, ldx, Wfold, ldw, C, ldc, M, N, K, true, duo_dbg());
     a.ln_stats = const_cast<float *>(stats); a.ln_slots = K / 64; a.ln_eps = eps; a.ln_s = ln_s; a.ln_c = ln_c;
     const int epi = act ? HGR_EPI_BIAS_QUICKGELU : HGR_EPI_BIAS;
-    const GemmLaunch L = k_tile.get() == 0 && p8_wanted(M, N, K)                           ? plan_p8(M, N, act)
-                         : k_ws.get() && k_tile.get() == 0 && ws_covers(M, N, K, WS_LNC) ? plan_ws(M, N, WS_LNC, epi, act)
-                                                                                          : plan_duo(a, 2, epi, false);
+    const GemmLaunch L = k_tile.get() == 0 && p8_wanted(M, N, K) ? plan_p8(M, N, act) : plan_duo(a, 2, epi, false);
     return gemm_run("hgr_gemm_nt_ln", a, &L, 1, dtype, stream);
 }
 

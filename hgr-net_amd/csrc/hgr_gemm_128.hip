@@ -36,8 +36,7 @@ __global__ __launch_bounds__(NT) void gemm_nt_128(GemmArgs p) {
     // XCD-aware, bijective remap of the 1-D grid (cdna_hip_programming.md T1)
     const int nwg = gridDim.x;
     const int orig = blockIdx.x;
-    const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const int wg = xcd_first_tile(nwg, orig & 7) + (orig >> 3);
     // Grouped raster inside the XCD's range: GROUP panels of the big operand stay L2-resident while
     // the walk slides over the other operand's panels, so ~GROUP concurrently running tiles share every
     // panel either way (64 tiles in flight per XCD = 8 x 8 panels of 128 x K: ~3 MB at K = 768 < 4 MB L2).

@@ -50,8 +50,7 @@ __global__ __launch_bounds__(NT256) void gemm_nt_256(GemmArgs p) {
 
     const int nwg = gridDim.x;
     const int orig = blockIdx.x;
-    const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const int wg = xcd_first_tile(nwg, orig & 7) + (orig >> 3);
     constexpr int GROUP = 4;      // 32 tiles in flight per XCD = 4 x 8 panels of 256 x K
     int tm, tn;
     if (p.m_fastest) {

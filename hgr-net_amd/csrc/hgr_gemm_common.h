@@ -54,7 +54,7 @@ struct GemmArgs {
     // HGR_EPI_QGELU_GRAD16 on gemm_nt_duo only (hgr_gemm_nt_qgelu_grad_colsum): column sums of the ROUNDED 16-bit outputs per 64-row
     // unit, colsum[unit][n] for unit < colsum_units = ceil(M / 64) - the bias gradient of the layer below without a second pass over C
     float *colsum = nullptr; int colsum_units = 0;
-    int total = 0;   // gemm_nt_duo, persistent form: number of virtual blocks (0 = gridDim.x, one tile per workgroup); gemm_nt_ws: its tile count
+    int total = 0;   // gemm_nt_duo, persistent form: number of virtual blocks (0 = gridDim.x, one tile per workgroup)
 };
 
 // The part of the argument block every host entry point fills alike; the entry point then sets only what is specific to it.
@@ -115,25 +115,17 @@ template <int DT, bool GELU> __device__ __forceinline__ u32x2 ln_out16(float2 mr
 // The folded LayerNorm's output through QuickGELU in 4 plain + 2 quarter-rate vector instructions per element (round 6; ln_apply +
 // quick_gelu: 5 + 2).  With k = -1.702 log2(e) and the row's rstd and the column's c pre-multiplied by k (once per row / column):
 //     w = k v  straight out of the second FMA,   e = 2^w,   v sigmoid(1.702 v) = v / (1 + e) = w / (k + k e)
-// Every folded-LayerNorm consumer with QuickGELU (gemm_nt_duo, gemm_nt_ws, gemm_nt_p8) goes through this function, so they keep
-// rounding alike.  -DHGR_QGELU_W=0 restores ln_apply + quick_gelu (A/B builds).
-#ifndef HGR_QGELU_W
-#define HGR_QGELU_W 1
-#endif
+// Every folded-LayerNorm consumer with QuickGELU (gemm_nt_duo, gemm_nt_p8) goes through this function, so they keep
+// rounding alike.
 constexpr float QG_K = -1.702f * 1.4426950408889634f;
 __device__ __forceinline__ float ln_apply_gelu(float2 mr, float acc, float s_n, float c_n) {
-#if HGR_QGELU_W
     const float w = __builtin_fmaf(mr.y * QG_K, __builtin_fmaf(-mr.x, s_n, acc), c_n * QG_K);
     return w * __builtin_amdgcn_rcpf(__builtin_fmaf(QG_K, __builtin_amdgcn_exp2f(w), QG_K));
-#else
-    return quick_gelu(ln_apply(mr, acc, s_n, c_n));
-#endif
 }
 
 template <int DT, bool GELU> __device__ __forceinline__ u32x2 ln_out16(float2 mr, f32x4 acc, f32x4 s4, f32x4 c4) {
     u32x2 o;
     if (GELU) {
-#if HGR_QGELU_W
         const float rk = mr.y * QG_K;
         float w[4], r[4];
 #pragma unroll
@@ -143,16 +135,6 @@ template <int DT, bool GELU> __device__ __forceinline__ u32x2 ln_out16(float2 mr
         }
         o[0] = mul_pack16<DT>(w[0], r[0], w[1], r[1]);
         o[1] = mul_pack16<DT>(w[2], r[2], w[3], r[3]);
-#else
-        float v[4], r[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[e] = ln_apply(mr, acc[e], s4[e], c4[e]);
-            r[e] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * v[e]));
-        }
-        o[0] = mul_pack16<DT>(v[0], r[0], v[1], r[1]);
-        o[1] = mul_pack16<DT>(v[2], r[2], v[3], r[3]);
-#endif
     } else {
         float u[4];
 #pragma unroll
@@ -268,22 +250,24 @@ __device__ __forceinline__ void store_quad_full(const GemmArgs &p, f32x4 v, f32x
 // LDS-DMA in its BUFFER form (buffer_load_dwordx4 ... offen lds): the per-lane source is a 32-bit byte offset into a buffer resource
 // (128-bit descriptor in SGPRs: base, no stride, 4 GB of records, raw dword format) and the K-tile advance rides in the scalar offset
 // operand - one address VGPR per instruction and no VALU, where the global form (global_load_lds_dwordx4) needs a 64-bit per-lane
-// pointer, i.e. a 64-bit add (two VALU) and two address VGPRs per instruction.  -DHGR_DMA_GLOBAL=1 builds the global form (A/B runs).
+// pointer, i.e. a 64-bit add (two VALU) and two address VGPRs per instruction.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t dma_rsrc(const void *base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)0xFFFFFFFFu, 0x00020000);
 }
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, const char *base, unsigned voff, int soff, char *lds_dst) {
-#if defined(HGR_DMA_GLOBAL) && HGR_DMA_GLOBAL
-    __builtin_amdgcn_global_load_lds((const AS1 void *)(base + soff + voff), (AS3 void *)lds_dst, 16, 0, 0);
-#else
+__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff, char *lds_dst) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (AS3 void *)lds_dst, 16, (int)voff, soff, 0, 0);
-#endif
 }
 
 // R interval end: my share of the piece the NEXT read interval needs has landed (counted vmcnt), my own
 // ds_reads are complete (so the slot they read may be refilled), then the barrier.  M interval end: barrier.
-#define HGR_RWAIT(N) do { __builtin_amdgcn_sched_barrier(0); \
-    asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)\n\ts_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+// rwait<N>(): the count as a constant expression (a loop shared by two tile shapes waits for MT + 4); HGR_RWAIT(N) is the same call.
+template <int N> __device__ __forceinline__ void rwait() {
+    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+#define HGR_RWAIT(N) hgr_gemm::rwait<N>()
 #define HGR_RBAR() do { __builtin_amdgcn_sched_barrier(0); \
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define HGR_MBAR() do { __builtin_amdgcn_sched_barrier(0); \
@@ -291,7 +275,8 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, const char *b
 
 
 // 16 MFMAs of a phase interleaved with NR LDS reads, NW LDS writes and NV vector-memory instructions (LDS-DMAs) that do not depend on
-// them: the scheduler is told to issue them in the gaps between MFMAs instead of in a block in front (gemm_nt_ws, -DHGR_DUO_PF=1)
+// them: the scheduler is told to issue them in the gaps between MFMAs instead of in a block in front (the fragment-prefetch loop of
+// gemm_nt_duo's LayerNorm consumers)
 template <int NR, int NW, int NV, int M_, int NM = 16>
 __device__ __forceinline__ void mfma16_interleave_step() {
     if constexpr (M_ < NM) {
@@ -309,6 +294,131 @@ __device__ __forceinline__ void mfma16_interleave() { mfma16_interleave_step<NR,
 template <int NR, int NW, int NV>
 __device__ __forceinline__ void mfma8_interleave() { mfma16_interleave_step<NR, NW, NV, 0, 8>(); }
 
+// ---- pieces more than one kernel of the family is built from: one copy each, so that what must round alike does --------------------
+
+// Tiles -> XCDs.  Workgroups b, b + 8, b + 16, ... run on XCD b & 7 and share its L2; the rasters give every XCD a CONTIGUOUS range of
+// the ntiles tile (or workgroup) ids, the first ntiles % 8 XCDs one more than the others: the first id of XCD xcd's range, and its length.
+__device__ __forceinline__ int xcd_first_tile(int ntiles, int xcd) {
+    const int q8 = ntiles >> 3, r8 = ntiles & 7;
+    return xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+}
+__device__ __forceinline__ int xcd_tile_count(int ntiles, int xcd) { return (ntiles >> 3) + (xcd < (ntiles & 7) ? 1 : 0); }
+
+// LayerNorm consumers: (sum, sum of squares) of one row from the producer's per-slot partial sums, sp = the row's `slots` pairs (two per
+// 16-byte load), summed in slot order.  The usual row widths get all their loads issued back to back (a load inside a run-time loop is
+// waited for on the spot: six dependent L2 round trips for width 768).  Callers clamp the row and call ln_finalize themselves.
+__device__ __forceinline__ void ln_row_sums(const f32x4 *sp, int slots, float &s1, float &s2) {
+    float a1 = 0.f, a2 = 0.f;
+    auto fixed = [&](auto nq_tag) {
+        constexpr int NQ = decltype(nq_tag)::value;
+        f32x4 t[NQ];
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) t[i] = sp[i];
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) { a1 += t[i][0] + t[i][2]; a2 += t[i][1] + t[i][3]; }
+    };
+    switch (slots) {
+        case 4: fixed(std::integral_constant<int, 2>()); break;      // width 256
+        case 8: fixed(std::integral_constant<int, 4>()); break;      // 512
+        case 10: fixed(std::integral_constant<int, 5>()); break;     // 640
+        case 12: fixed(std::integral_constant<int, 6>()); break;     // 768
+        case 16: fixed(std::integral_constant<int, 8>()); break;     // 1024
+        default:
+            for (int i = 0; i < slots / 2; ++i) { const f32x4 t = sp[i]; a1 += t[0] + t[2]; a2 += t[1] + t[3]; }
+    }
+    s1 = a1; s2 = a2;
+}
+
+// Residual producers (gemm_nt_duo with LN = 1, gemm_nt_res_wide): one pass of the epilogue on a lane's 8 consecutive columns of a row.
+// The kernels keep their own loads, stores, buffer ring and pass order; the arithmetic is here.
+// new x = (acc + bias) + old x, the old x decoded from the pair (pair_dec4: hi's bits + the low byte's 8 mantissa bits)
+template <int DT> __device__ __forceinline__ void pair_pass_values(f32x4 lo4, f32x4 hi4, f32x4 b8lo, f32x4 b8hi, typename T16<DT>::vec8 oh, u32x2 ol, float (&v)[8]) {
+    v[0] = (lo4[0] + b8lo[0]) + pair_dec4<DT, 0>(oh[0], ol[0]); v[1] = (lo4[1] + b8lo[1]) + pair_dec4<DT, 1>(oh[1], ol[0]);
+    v[2] = (lo4[2] + b8lo[2]) + pair_dec4<DT, 2>(oh[2], ol[0]); v[3] = (lo4[3] + b8lo[3]) + pair_dec4<DT, 3>(oh[3], ol[0]);
+    v[4] = (hi4[0] + b8hi[0]) + pair_dec4<DT, 0>(oh[4], ol[1]); v[5] = (hi4[1] + b8hi[1]) + pair_dec4<DT, 1>(oh[5], ol[1]);
+    v[6] = (hi4[2] + b8hi[2]) + pair_dec4<DT, 2>(oh[6], ol[1]); v[7] = (hi4[3] + b8hi[3]) + pair_dec4<DT, 3>(oh[7], ol[1]);
+}
+// the new pair of those 8 values: pair_split()'s bits through pair_split2 / pair_put_q (hgr_common.h), ~5 instead of ~8 vector
+// instructions per element
+template <int DT> __device__ __forceinline__ void pair_pass_split(const float (&v)[8], u32x4 &nh, u32x2 &nl) {
+    unsigned tq[8];
+#pragma unroll
+    for (int e2 = 0; e2 < 4; ++e2) nh[e2] = pair_split2<DT>(v[2 * e2], v[2 * e2 + 1], tq[2 * e2], tq[2 * e2 + 1]);
+    unsigned n0, n1;
+    pair_put_q<DT, 0>(n0, tq[0]); pair_put_q<DT, 1>(n0, tq[1]); pair_put_q<DT, 2>(n0, tq[2]); pair_put_q<DT, 3>(n0, tq[3]);
+    pair_put_q<DT, 0>(n1, tq[4]); pair_put_q<DT, 1>(n1, tq[5]); pair_put_q<DT, 2>(n1, tq[6]); pair_put_q<DT, 3>(n1, tq[7]);
+    nl = (u32x2){n0, n1};
+}
+// their share of the slot's (sum, sum of squares): the pairing of the 4-column form, stage by stage
+__device__ __forceinline__ void pair_pass_sums(const float (&v)[8], float &s1, float &s2) {
+    s1 = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+    s2 = (__builtin_fmaf(v[0], v[0], v[1] * v[1]) + __builtin_fmaf(v[2], v[2], v[3] * v[3])) +
+         (__builtin_fmaf(v[4], v[4], v[5] * v[5]) + __builtin_fmaf(v[6], v[6], v[7] * v[7]));
+}
+// ... and the slot's totals over the 8 lanes of a row (64 columns), for the two rows of a pass: three DPP stages, the four chains
+// advancing together (DPP latencies overlap); every lane of the row ends with the totals
+template <int CTRL> __device__ __forceinline__ void pair_pass_dpp_stage(float (&s1)[2], float (&s2)[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        s1[q] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s1[q]), CTRL, 0xF, 0xF, true));
+        s2[q] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s2[q]), CTRL, 0xF, 0xF, true));
+    }
+}
+__device__ __forceinline__ void pair_pass_reduce(float (&s1)[2], float (&s2)[2]) {
+    pair_pass_dpp_stage<0xB1>(s1, s2); pair_pass_dpp_stage<0x4E>(s1, s2); pair_pass_dpp_stage<0x141>(s1, s2);
+}
+
+// One K-tile of the 8-wave ping-pong loop whose phases split a wave's 128 columns (gemm_nt_p8: MT = 4 m tiles per wave, gemm_nt_res_wide:
+// MT = 5).  st = the K-tile's stage; PA / PW0 / PW1 = the pieces' offsets inside a stage; issue1 / issue2 = the caller's LDS-DMA issue
+// for the phases (PW1(t+1), MT-independent 2 instructions; PA(t+2) + PW0(t+2), MT + 2): a count = "my N youngest may still be in flight".
+//     ph1(t): reads A (2 MT x ds_read_b128), W columns 0-63 (8 x)    issue1 behind the reads    waits vmcnt(MT + 4): PW1(t) landed
+//     ph2(t): reads W columns 64-127 (8 x), A fragments stay          issue2 behind the reads    waits vmcnt(MT + 4): PA(t+1), PW0(t+1) landed
+// MODE 0: steady state (t + 2 < nk), 1: second-last K-tile (issue1 only), 2: last K-tile (no issue)
+template <int DT, int MT, int MODE, int PA, int PW0, int PW1, typename Issue1, typename Issue2>
+__device__ __forceinline__ void pingpong_ktile(const char *st, int offA, int offW, int sw0, int sw1, f32x4 (&acc)[MT][8],
+                                               typename T16<DT>::vec8 (&wf)[4][2], typename T16<DT>::vec8 (&af)[MT][2], Issue1 issue1, Issue2 issue2) {
+    typedef typename T16<DT>::vec8 vec8;
+    // ---- ph1: all rows of the wave x its columns 0-63 ----
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        wf[j][0] = *(const vec8 *)(st + PW0 + offW + j * 2048 + sw0);
+        wf[j][1] = *(const vec8 *)(st + PW0 + offW + j * 2048 + sw1);
+    }
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+        af[i][0] = *(const vec8 *)(st + PA + offA + i * 2048 + sw0);
+        af[i][1] = *(const vec8 *)(st + PA + offA + i * 2048 + sw1);
+    }
+    if (MODE <= 1) issue1();                                   // behind the reads; its slot was last read in ph2(t - 1), two barriers ago
+    if (MODE <= 1) rwait<MT + 4>(); else rwait<0>();           // PW1(t) landed
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = T16<DT>::mfma16(wf[j][kk], af[i][kk], acc[i][j]);
+    __builtin_amdgcn_s_setprio(0);
+    HGR_MBAR();
+    // ---- ph2: columns 64-127, the A fragments stay ----
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        wf[j][0] = *(const vec8 *)(st + PW1 + offW + j * 2048 + sw0);
+        wf[j][1] = *(const vec8 *)(st + PW1 + offW + j * 2048 + sw1);
+    }
+    if (MODE == 0) issue2();                                   // read in ph1(t), two barriers ago
+    if (MODE == 0) rwait<MT + 4>(); else if (MODE == 1) rwait<2>(); else HGR_RBAR();      // PA(t+1), PW0(t+1) landed
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][4 + j] = T16<DT>::mfma16(wf[j][kk], af[i][kk], acc[i][4 + j]);
+    __builtin_amdgcn_s_setprio(0);
+    HGR_MBAR();
+}
+
 // ---- launchers, one per translation unit (the kernels are templates; host code selects by value) ------------------------
 enum { V128_PLAIN = 0, V128_TALL = 1, V128_CONV = 2, V128_CONV_TALL = 3 };
 // gemm_nt_128 family.  PLAIN: epi any (K == 64 with 16-bit bias epilogues takes the one-stage variant); TALL: 256 x 64 tiles,
@@ -319,13 +429,6 @@ void launch_256(const GemmArgs &a, int dtype, int epi, bool out32, bool conv, di
 // gemm_nt_duo: ln = 0 plain (any epi), 1 LayerNorm producer, 2 LayerNorm consumer (epi BIAS / BIAS_QUICKGELU), 4 dual output
 // (pre-activation + QuickGELU), 5 the 3 x 3 convolution.  ln = 1 walks a.total > grid.x virtual blocks (plan_duo, hgr_gemm.hip)
 void launch_duo(const GemmArgs &a, int dtype, int epi, bool out32, int ln, dim3 grid, hipStream_t s);
-// gemm_nt_ws (hgr_gemm_ws.hip): 256 x 128 tiles, ONE persistent workgroup per CU of 4 matrix waves + 4 helper waves; the epilogue of
-// tile i runs in the helper waves under the MFMAs of tile i + 1.  Same bits as gemm_nt_duo.  mode WS_PLAIN: 16-bit C = act(A W^T
-// [+ bias]), act 0 none / 1 QuickGELU / 2 ReLU; WS_LNC: the folded-LayerNorm consumer (act 0 / 1); WS_LNP: the residual producer.
-enum { WS_PLAIN = 0, WS_LNC = 1, WS_LNP = 2 };
-bool ws_covers(int M, int N, int K, int mode);      // whole tiles, an even number >= 12 of K-tiles, at least one tile per CU
-int ws_cus();                         // workgroups of a launch: the CUs in whole multiples of the 8 XCDs
-void launch_ws(const GemmArgs &a, int dtype, int mode, int act, bool hasb, dim3 grid, hipStream_t s);
 // hgr_gemm_p8.hip: the LayerNorm-folded consumer as one persistent 512-thread workgroup per CU on 256 x 256 tiles
 bool p8_covers(int M, int N, int K);
 void launch_p8(const GemmArgs &a, int dtype, int act, dim3 grid, hipStream_t s);

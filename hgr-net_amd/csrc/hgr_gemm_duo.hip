@@ -25,9 +25,6 @@
 
 namespace hgr_gemm {
 
-#ifndef HGR_PAIR_V2
-#define HGR_PAIR_V2 1           // 0: the round-5 form of the producer's pair split (A/B builds)
-#endif
 constexpr int NTD = 256;
 constexpr int DUO_A0 = 0, DUO_A1 = 32768, DUO_W0 = 65536, DUO_W1 = 73728, DUO_LDS = 81920;
 
@@ -118,13 +115,13 @@ __device__ __forceinline__ void duo_tile(const GemmArgs &p, char *smem, const in
             return;
         }
 #pragma unroll
-        for (int i = 2 * h; i < 2 * h + 2; ++i) dma16(rA, p.A, off[i], t * 128, dst + i * 4096);
+        for (int i = 2 * h; i < 2 * h + 2; ++i) dma16(rA, off[i], t * 128, dst + i * 4096);
     };
     auto issueW = [&](const unsigned (&off)[2], int slot_base, int t) {
         if (HGR_LAB_ON((p.dbg & 512) && t > 1)) return;
         char *dst = ldsw + slot_base;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dma16(rW, p.W, off[i], t * 128, dst + i * 4096);
+        for (int i = 0; i < 2; ++i) dma16(rW, off[i], t * 128, dst + i * 4096);
     };
 
     f32x4 acc[MH][2][4][2];     // [m-half][n-half][m tile][n tile]
@@ -146,26 +143,8 @@ __device__ __forceinline__ void duo_tile(const GemmArgs &p, char *smem, const in
     // by the partner workgroup); at kernel entry it would delay the first LDS-DMA by a memory round trip.
     auto ln_row_stats = [&]() {
         const f32x4 *sp = (const f32x4 *)(p.ln_stats + (int64_t)min(m0 + tid, p.M - 1) * p.ln_slots * 2);
-        float s1 = 0.f, s2 = 0.f;
-        // the usual row widths get all their loads issued back to back (a load inside a run-time loop is waited for on the spot:
-        // six dependent L2 round trips for width 768)
-        auto fixed = [&](auto nq_tag) {
-            constexpr int NQ = decltype(nq_tag)::value;
-            f32x4 t[NQ];
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) t[i] = sp[i];
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) { s1 += t[i][0] + t[i][2]; s2 += t[i][1] + t[i][3]; }
-        };
-        switch (p.ln_slots) {
-            case 4: fixed(std::integral_constant<int, 2>()); break;      // width 256
-            case 8: fixed(std::integral_constant<int, 4>()); break;      // 512
-            case 10: fixed(std::integral_constant<int, 5>()); break;     // 640
-            case 12: fixed(std::integral_constant<int, 6>()); break;     // 768
-            case 16: fixed(std::integral_constant<int, 8>()); break;     // 1024
-            default:
-                for (int i = 0; i < p.ln_slots / 2; ++i) { const f32x4 t = sp[i]; s1 += t[0] + t[2]; s2 += t[1] + t[3]; }
-        }
+        float s1, s2;
+        ln_row_sums(sp, p.ln_slots, s1, s2);
         return ln_finalize(s1, s2, 1.0f / (float)p.K, p.ln_eps);
     };
     const int nk = p.K / 64;    // >= 2 (host guarantees)
@@ -176,19 +155,12 @@ __device__ __forceinline__ void duo_tile(const GemmArgs &p, char *smem, const in
     // Fragment PREFETCH form of the main loop (round 5), compiled into the folded-LayerNorm consumers (LN = 2: c_fc, in_proj, the
     // k / v projection of the last block): measured in the ViT-B/32 step, same box, three interleaved pairs: c_fc 140.4 / 140.1 / 139.3
     // -> 136.9 / 137.0 / 136.5 us, kv 73.5 -> 70.8; the residual producers and the patch GEMM lose 2 - 4 % with it (their epilogue
-    // and tail plan want the registers), so they keep the loop below.  -DHGR_DUO_PF=1 compiles it into every instantiation, =0 into none.
-#ifndef HGR_DUO_PF
-#define HGR_DUO_PF 2
-#endif
-#ifndef HGR_DUO_PF_DMA_FIRST
-#define HGR_DUO_PF_DMA_FIRST 0      // experiment: 1 = a region's LDS-DMAs in front of its MFMAs instead of in their gaps
-#endif
-    constexpr bool PF_BUILD = HGR_DUO_PF == 1 || (HGR_DUO_PF == 2 && LN == 2);
+    // and tail plan want the registers), so they keep the loop below.
+    constexpr bool PF_BUILD = LN == 2;
     const bool pf_tile = MH == 2 && !CONV && PF_BUILD && m0 + 256 <= p.M && n0 + 128 <= p.N && (p.K & 127) == 0 && p.K >= 256;
     if (pf_tile) {
       if constexpr (MH == 2 && !CONV && PF_BUILD) {
-        // The main loop of gemm_nt_ws's matrix waves inside the two-workgroup kernel - fragments
-        // prefetched ONE PHASE AHEAD into a second register set (Gray-code quadrant walk alternating between even and odd K-tiles: four
+        // Fragments prefetched ONE PHASE AHEAD into a second register set (Gray-code quadrant walk alternating between even and odd K-tiles: four
         // fragment sets), reads / DMA issue interleaved with the MFMAs, so that no MFMA burst starts with a wait for its own LDS reads.
         //     ph1: Q(X, W0)   prefetch Y(t)                issues W0(t+1) x2, X'(t+2) x4     wait: W1(t) landed      (vmcnt 6)
         //     ph2: Q(Y, W0)   prefetch W1(t)               issues Y'(t+2) x4
@@ -234,12 +206,12 @@ __device__ __forceinline__ void duo_tile(const GemmArgs &p, char *smem, const in
         auto pfA = [&](int half, int slot_base, int tt) {            // half 0 = piece A0 (m-half 0 rows), 1 = A1
             char *dst = ldsw + slot_base + (tt & 1) * 16384;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dma16(rA, p.A, laneA, tt * 128 + ((i >> 1) * 128 + (i & 1) * 32 + half * 64) * rowA, dst + i * 4096);
+            for (int i = 0; i < 4; ++i) dma16(rA, laneA, tt * 128 + ((i >> 1) * 128 + (i & 1) * 32 + half * 64) * rowA, dst + i * 4096);
         };
         auto pfW = [&](int half, int slot_base, int tt) {
             char *dst = ldsw + slot_base;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) dma16(rW, p.W, laneW, tt * 128 + (i * 64 + half * 32) * rowW, dst + i * 4096);
+            for (int i = 0; i < 2; ++i) dma16(rW, laneW, tt * 128 + (i * 64 + half * 32) * rowW, dst + i * 4096);
         };
         // issue order of the steady state: ... A0(0), A1(0), W0(0) | A1(1), A0(1), W1(0)
         pfA(0, DUO_A0, 0); pfA(1, DUO_A1, 0); pfW(0, DUO_W0, 0);
@@ -257,11 +229,11 @@ __device__ __forceinline__ void duo_tile(const GemmArgs &p, char *smem, const in
             // ---- ph1 ----
             if (MODE <= 1) pfW(0, DUO_W0, t + 1);
             if (ODD) { rdA2(afA, DUO_A0 + cb, 0); mmk(acc[1][0], wf0, afB, 0); } else { rdA2(afB, DUO_A1 + cb, 0); mmk(acc[0][0], wf0, afA, 0); }
-            if (MODE <= 1) mfma8_interleave<4, 0, HGR_DUO_PF_DMA_FIRST ? 0 : 2>(); else mfma8_interleave<4, 0, 0>();
+            if (MODE <= 1) mfma8_interleave<4, 0, 2>(); else mfma8_interleave<4, 0, 0>();
             __builtin_amdgcn_sched_barrier(0);
             if (MODE == 0) pfA(ODD ? 1 : 0, ODD ? DUO_A1 : DUO_A0, t + 2);
             if (ODD) { rdA2(afA, DUO_A0 + cb, 1); mmk(acc[1][0], wf0, afB, 1); } else { rdA2(afB, DUO_A1 + cb, 1); mmk(acc[0][0], wf0, afA, 1); }
-            if (MODE == 0) mfma8_interleave<4, 0, HGR_DUO_PF_DMA_FIRST ? 0 : 4>(); else mfma8_interleave<4, 0, 0>();
+            if (MODE == 0) mfma8_interleave<4, 0, 4>(); else mfma8_interleave<4, 0, 0>();
             if (MODE == 0) HGR_RWAIT(6); else if (MODE == 1) HGR_RWAIT(2); else HGR_RWAIT(0);
             // ---- ph2 ----
             rdW(wf1, DUO_W1);
@@ -270,14 +242,14 @@ __device__ __forceinline__ void duo_tile(const GemmArgs &p, char *smem, const in
             __builtin_amdgcn_sched_barrier(0);
             if (MODE == 0) pfA(ODD ? 0 : 1, ODD ? DUO_A0 : DUO_A1, t + 2);
             if (ODD) mmk(acc[0][0], wf0, afA, 1); else mmk(acc[1][0], wf0, afB, 1);
-            if (MODE == 0) mfma8_interleave<0, 0, HGR_DUO_PF_DMA_FIRST ? 0 : 4>();
+            if (MODE == 0) mfma8_interleave<0, 0, 4>();
             HGR_RBAR();
             // ---- ph3 ----
             if (ODD) mmk(acc[0][1], wf1, afA, 0); else mmk(acc[1][1], wf1, afB, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (MODE <= 1) pfW(1, DUO_W1, t + 1);
             if (ODD) mmk(acc[0][1], wf1, afA, 1); else mmk(acc[1][1], wf1, afB, 1);
-            if (MODE <= 1) mfma8_interleave<0, 0, HGR_DUO_PF_DMA_FIRST ? 0 : 2>();
+            if (MODE <= 1) mfma8_interleave<0, 0, 2>();
             if (MODE == 0) HGR_RWAIT(10); else if (MODE == 1) HGR_RWAIT(2); else HGR_RBAR();
             // ---- ph4 ----
             if (MODE <= 1) { rdW(wf0, DUO_W0); if (ODD) rdA2(afA, DUO_A0 + nb, 0); else rdA2(afB, DUO_A1 + nb, 0); }
@@ -402,12 +374,12 @@ __device__ __forceinline__ void duo_tile(const GemmArgs &p, char *smem, const in
                 return;
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dma16(rA, p.A, oA0[i], t * 128, dst + i * 4096);
+            for (int i = 0; i < 4; ++i) dma16(rA, oA0[i], t * 128, dst + i * 4096);
         };
         auto issueWh = [&](const unsigned (&off)[2], int slot_base, int t) {
             char *dst = ldsw + slot_base + (t & 1) * 8192;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) dma16(rW, p.W, off[i], t * 128, dst + i * 4096);
+            for (int i = 0; i < 2; ++i) dma16(rW, off[i], t * 128, dst + i * 4096);
         };
         // prologue in steady-state order: A(0), W0(0), W1(0), A(1), W0(1)
         issueAh(0, 0); issueWh(oW0, HW0, 0); issueWh(oW1, HW1, 0); issueAh(1, 1); issueWh(oW0, HW0, 1);
@@ -701,59 +673,16 @@ __device__ __forceinline__ void duo_tile(const GemmArgs &p, char *smem, const in
                     const vec8 oh = __builtin_bit_cast(vec8, ohb[pb][q]);
                     const u32x2 ol = olb[pb][q];
                     float v[8];
-#if HGR_PAIR_V2
-                    // (acc + bias) + old x (pair_dec4: hi's bits + the low byte's 8 mantissa bits)
-                    v[0] = (lo4[0] + b8lo[0]) + pair_dec4<DT, 0>(oh[0], ol[0]); v[1] = (lo4[1] + b8lo[1]) + pair_dec4<DT, 1>(oh[1], ol[0]);
-                    v[2] = (lo4[2] + b8lo[2]) + pair_dec4<DT, 2>(oh[2], ol[0]); v[3] = (lo4[3] + b8lo[3]) + pair_dec4<DT, 3>(oh[3], ol[0]);
-                    v[4] = (hi4[0] + b8hi[0]) + pair_dec4<DT, 0>(oh[4], ol[1]); v[5] = (hi4[1] + b8hi[1]) + pair_dec4<DT, 1>(oh[5], ol[1]);
-                    v[6] = (hi4[2] + b8hi[2]) + pair_dec4<DT, 2>(oh[6], ol[1]); v[7] = (hi4[3] + b8hi[3]) + pair_dec4<DT, 3>(oh[7], ol[1]);
-#else
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {              // (acc + bias) + old x (pair_dec: hi's bits + the low byte's 8 mantissa bits)
-                        v[e] = (lo4[e] + b8lo[e]) + pair_dec<DT>(oh[e], (ol[0] >> (8 * e)) & 255u);
-                        v[e + 4] = (hi4[e] + b8hi[e]) + pair_dec<DT>(oh[e + 4], (ol[1] >> (8 * e)) & 255u);
-                    }
-#endif
-#if HGR_PAIR_V2
-                    // pair_split()'s bits through pair_split2 / pair_put_q (hgr_common.h): ~5 instead of ~8 vector instructions per element
+                    pair_pass_values<DT>(lo4, hi4, b8lo, b8hi, oh, ol, v);
                     u32x4 nh;
                     u32x2 nl;
-                    {
-                        unsigned tq[8];
-#pragma unroll
-                        for (int e2 = 0; e2 < 4; ++e2) nh[e2] = pair_split2<DT>(v[2 * e2], v[2 * e2 + 1], tq[2 * e2], tq[2 * e2 + 1]);
-                        unsigned n0, n1;
-                        pair_put_q<DT, 0>(n0, tq[0]); pair_put_q<DT, 1>(n0, tq[1]); pair_put_q<DT, 2>(n0, tq[2]); pair_put_q<DT, 3>(n0, tq[3]);
-                        pair_put_q<DT, 0>(n1, tq[4]); pair_put_q<DT, 1>(n1, tq[5]); pair_put_q<DT, 2>(n1, tq[6]); pair_put_q<DT, 3>(n1, tq[7]);
-                        nl = (u32x2){n0, n1};
-                    }
+                    pair_pass_split<DT>(v, nh, nl);
                     *(u32x4 *)(hw + (xo + (rl + q * 8) * ldxB)) = nh;
-#else
-                    vec8 nh;
-                    u32x2 nl = (u32x2){0u, 0u};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        unsigned q0, q1;
-                        E h0, h1;
-                        pair_split<DT>(v[e], h0, q0);
-                        pair_split<DT>(v[e + 4], h1, q1);
-                        nh[e] = h0; nh[e + 4] = h1;
-                        nl[0] |= q0 << (8 * e);
-                        nl[1] |= q1 << (8 * e);
-                    }
-                    *(u32x4 *)(hw + (xo + (rl + q * 8) * ldxB)) = __builtin_bit_cast(u32x4, nh);
-#endif
                     if (!HGR_LAB_ON(p.dbg & 64)) *(u32x2 *)(lw + (lo8 + (rl + q * 8) * ldlB)) = nl;
-                    s1[q] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                    s2[q] = (__builtin_fmaf(v[0], v[0], v[1] * v[1]) + __builtin_fmaf(v[2], v[2], v[3] * v[3])) +
-                            (__builtin_fmaf(v[4], v[4], v[5] * v[5]) + __builtin_fmaf(v[6], v[6], v[7] * v[7]));
+                    pair_pass_sums(v, s1[q], s2[q]);
                 }
                 if (HGR_LAB_ON(p.dbg & 32)) continue;
-#define HGR_DPP_STAGE8(CTRL) _Pragma("unroll") for (int q = 0; q < 2; ++q) { \
-                    s1[q] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s1[q]), CTRL, 0xF, 0xF, true)); \
-                    s2[q] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s2[q]), CTRL, 0xF, 0xF, true)); }
-                HGR_DPP_STAGE8(0xB1) HGR_DPP_STAGE8(0x4E) HGR_DPP_STAGE8(0x141)
-#undef HGR_DPP_STAGE8
+                pair_pass_reduce(s1, s2);
                 if (c8 == 0) {
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
@@ -981,8 +910,7 @@ __global__ __launch_bounds__(NTD, 2) void gemm_nt_duo(GemmArgs p) {
     const int nwg = half ? total - p.nbig : p.nbig;
     const int orig = half ? vb - p.nbig : vb;
     const int tiles_m = half ? p.tiles_m_half : p.big_panels;
-    const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const int wg = xcd_first_tile(nwg, orig & 7) + (orig >> 3);
     const int GROUP = p.group;    // default 4: 64 tiles in flight per XCD = 4 row panels of 256 x 16 column panels of 128
     int tm, tn;
     if (p.m_fastest) {

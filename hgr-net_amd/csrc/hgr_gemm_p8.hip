@@ -17,7 +17,8 @@
 // (a phase's LDS-DMAs behind its reads: an LDS-DMA can stall at the CU's one address path; the split by COLUMNS balances the phases'
 // LDS time - 16 + 8 reads where a split by rows has 20 + 4 against MFMA bursts of equal length)
 // 32 MFMAs per wave and phase; waves 0-3 and 4-7 (one of each per SIMD) run one barrier interval apart.  Same operand roles and K order
-// per output element as gemm_nt_duo, hence the same accumulator bits; the epilogue is its consumer epilogue, expression for expression.
+// per output element as gemm_nt_duo, hence the same accumulator bits; the epilogue rounds through the same ln_row_sums / ln_finalize / ln_out16 (hgr_gemm_common.h).
+// The K-tile itself is pingpong_ktile (hgr_gemm_common.h), shared with gemm_nt_res_wide.
 //
 // Persistent: a workgroup walks its XCD's contiguous range of tiles (column tiles fastest: the tiles in flight on an L2 share row
 // panels).  The next tile's first K-tile is requested into stage 0 BEFORE the epilogue, which stages the converted tile through the
@@ -54,9 +55,9 @@ __global__ __launch_bounds__(P8_NT) void gemm_nt_p8(GemmArgs p) {
     // tiles -> workgroups: tile id = row tile * tiles_n + column tile; every XCD (blocks b, b + 8, ... share an L2) owns a contiguous
     // range of ids and its workgroups walk it with a stride of the XCD's workgroup count
     const int ntiles = p.tiles_m * p.tiles_n, orig = blockIdx.x, G = gridDim.x;
-    const int xcd = orig & 7, q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int xbase = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8, xcnt = q8 + (xcd < r8 ? 1 : 0);
-    const int xwgs = (G >> 3) + (xcd < (G & 7) ? 1 : 0);
+    const int xcd = orig & 7;
+    const int xbase = xcd_first_tile(ntiles, xcd), xcnt = xcd_tile_count(ntiles, xcd);
+    const int xwgs = xcd_tile_count(G, xcd);
     int cur = orig >> 3;
     if (cur >= xcnt) return;
 
@@ -87,12 +88,12 @@ __global__ __launch_bounds__(P8_NT) void gemm_nt_p8(GemmArgs p) {
     auto issueA = [&](int t) {
         char *dst = ldsw + (t & 1) * P8_STAGE + P8_PA;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dma16(rA, p.A, oA[i], t * 128, dst + i * 8192);
+        for (int i = 0; i < 4; ++i) dma16(rA, oA[i], t * 128, dst + i * 8192);
     };
     auto issueW = [&](const unsigned (&off)[2], int piece, int t) {
         char *dst = ldsw + (t & 1) * P8_STAGE + piece;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dma16(rW, p.W, off[i], t * 128, dst + i * 8192);
+        for (int i = 0; i < 2; ++i) dma16(rW, off[i], t * 128, dst + i * 8192);
     };
 
     const int nk = p.K / 64;    // even, >= 4 (host)
@@ -116,49 +117,10 @@ __global__ __launch_bounds__(P8_NT) void gemm_nt_p8(GemmArgs p) {
     HGR_RWAIT(8);
     if (wn) HGR_MBAR();         // ping-pong: group 1 runs one barrier interval behind group 0
 
-    // MODE 0: steady state (t + 2 < nk), 1: second-last K-tile, 2: last K-tile
+    // the shared K-tile (pingpong_ktile, hgr_gemm_common.h): ph1 issues PW1(t+1), ph2 PA(t+2) and PW0(t+2)
     auto ktile = [&](int t, auto mode_tag) {
-        constexpr int MODE = decltype(mode_tag)::value;
-        const char *st = smem + (t & 1) * P8_STAGE;
-        // ---- ph1: all 64 rows of the wave x its columns 0-63 ----
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            wf[j][0] = *(const vec8 *)(st + P8_PW0 + offW + j * 2048 + sw0);
-            wf[j][1] = *(const vec8 *)(st + P8_PW0 + offW + j * 2048 + sw1);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            af[i][0] = *(const vec8 *)(st + P8_PA + offA + i * 2048 + sw0);
-            af[i][1] = *(const vec8 *)(st + P8_PA + offA + i * 2048 + sw1);
-        }
-        if (MODE <= 1) issueW(oW1, P8_PW1, t + 1);              // behind the reads; its slot was last read in ph2(t - 1), two barriers ago
-        if (MODE <= 1) HGR_RWAIT(8); else HGR_RWAIT(0);         // PW1(t) landed
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = T16<DT>::mfma16(wf[j][kk], af[i][kk], acc[i][j]);
-        __builtin_amdgcn_s_setprio(0);
-        HGR_MBAR();
-        // ---- ph2: columns 64-127, the A fragments stay ----
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            wf[j][0] = *(const vec8 *)(st + P8_PW1 + offW + j * 2048 + sw0);
-            wf[j][1] = *(const vec8 *)(st + P8_PW1 + offW + j * 2048 + sw1);
-        }
-        if (MODE == 0) { issueA(t + 2); issueW(oW0, P8_PW0, t + 2); }     // read in ph1(t), two barriers ago
-        if (MODE == 0) HGR_RWAIT(8); else if (MODE == 1) HGR_RWAIT(2); else HGR_RBAR();      // PA(t+1), PW0(t+1) landed
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][4 + j] = T16<DT>::mfma16(wf[j][kk], af[i][kk], acc[i][4 + j]);
-        __builtin_amdgcn_s_setprio(0);
-        HGR_MBAR();
+        pingpong_ktile<DT, 4, decltype(mode_tag)::value, P8_PA, P8_PW0, P8_PW1>(smem + (t & 1) * P8_STAGE, offA, offW, sw0, sw1, acc, wf, af,
+            [&]() { issueW(oW1, P8_PW1, t + 1); }, [&]() { issueA(t + 2); issueW(oW0, P8_PW0, t + 2); });
     };
     for (int t = 0; t < nk - 2; ++t) ktile(t, std::integral_constant<int, 0>());
     ktile(nk - 2, std::integral_constant<int, 1>());
@@ -177,24 +139,8 @@ __global__ __launch_bounds__(P8_NT) void gemm_nt_p8(GemmArgs p) {
     const int le = tid_e & 63, re = le & 15, ge = le >> 4;
     if (tid_e < 256) {
         const f32x4 *sp = (const f32x4 *)(p.ln_stats + (int64_t)(m0c + tid_e) * p.ln_slots * 2);
-        float s1 = 0.f, s2 = 0.f;
-        auto fixed = [&](auto nq_tag) {
-            constexpr int NQ = decltype(nq_tag)::value;
-            f32x4 t[NQ];
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) t[i] = sp[i];
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) { s1 += t[i][0] + t[i][2]; s2 += t[i][1] + t[i][3]; }
-        };
-        switch (p.ln_slots) {
-            case 4: fixed(std::integral_constant<int, 2>()); break;
-            case 8: fixed(std::integral_constant<int, 4>()); break;
-            case 10: fixed(std::integral_constant<int, 5>()); break;
-            case 12: fixed(std::integral_constant<int, 6>()); break;
-            case 16: fixed(std::integral_constant<int, 8>()); break;
-            default:
-                for (int i = 0; i < p.ln_slots / 2; ++i) { const f32x4 t = sp[i]; s1 += t[0] + t[2]; s2 += t[1] + t[3]; }
-        }
+        float s1, s2;
+        ln_row_sums(sp, p.ln_slots, s1, s2);
         const float2 mr = ln_finalize(s1, s2, 1.0f / (float)p.K, p.ln_eps);
         const p8_f2 mv = {mr.x, mr.y};
         asm volatile("ds_write_b64 %0, %1" ::"v"(smem_a + P8_LN + tid_e * 8), "v"(mv) : "memory");

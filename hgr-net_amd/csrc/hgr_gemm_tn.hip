@@ -19,7 +19,7 @@
 // Tile 128 (a) x 128 (b) x 64 (m) per stage, 4 waves as 2 x 2, each 64 x 64 = 4 x 4 tiles of v_mfma_f32_16x16x32, two
 // LDS stages (64 KB), blockIdx.y = reduction slice.  EXEC is all ones at every transposing read (no divergent code
 // around them), as the ISA requires.
-#include "hgr_common.h"
+#include "hgr_gemm_common.h"
 #include <stdlib.h>
 
 #pragma clang diagnostic ignored "-Winline-asm"   // the LDS-DMA assembly below names m0 as clobbered (reserved register: hipcc warns)
@@ -203,8 +203,7 @@ __global__ __launch_bounds__(512) void gemm_tn_256(TnArgs p) {
     // one slice - 2-3 P panels and one set of Q panels for ~64 panel reads - where dealing tiles b, b + 8, ... of every slice to it made
     // each XCD fetch 7 panels per 12 reads, five slices at once.
     const int nwg = gridDim.x, orig = blockIdx.x;
-    const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const int wg = hgr_gemm::xcd_first_tile(nwg, orig & 7) + (orig >> 3);
     const int tiles = ((p.Na + 255) >> 8) * p.tiles_b;
     const int slice = wg / tiles, tile = wg - slice * tiles;
     const int ta = tile / p.tiles_b, tb = tile - ta * p.tiles_b;

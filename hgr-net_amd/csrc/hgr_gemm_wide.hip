@@ -1,7 +1,7 @@
 // =================================================================================================
 // gemm_nt_res_wide: the residual producer (hgr_gemm_nt_res_stats: (xh, xl) += A W^T + bias on the 16-bit-plus-byte pair, + the slot
-// statistics of the new rows) on 320 (M) x 256 (N) tiles, ONE 512-thread workgroup per tile and per CU, one round - the main loop of
-// gemm_nt_p8 (hgr_gemm_p8.hip) with a fifth m tile per wave and the producer epilogue of gemm_nt_duo in place of the consumer's.
+// statistics of the new rows) on 320 (M) x 256 (N) tiles, ONE 512-thread workgroup per tile and per CU, one round - the K-tile loop
+// gemm_nt_p8 runs (pingpong_ktile, hgr_gemm_common.h) with a fifth m tile per wave, and the producer pass of gemm_nt_duo (pair_pass_*).
 //
 // Why a third form of this product: ViT-B/32's c_proj at batch 512 is 25 600 x 768 x 3 072.  On gemm_nt_duo's 256 x 128 tiles that is
 // 600 tiles for 512 workgroup slots - a full round, then a tail of half tiles on a third of the slots (duo_plan, hgr_gemm.hip) - and a
@@ -24,7 +24,7 @@
 // scalar offset with the K advance.  The buffer descriptors start at the TILE's first row, so a lane keeps two offsets (A, W) in all.
 //
 // One tile per workgroup, no next-tile request: behind the last K-tile no DMA is in flight, and the epilogue is plain C++ over the
-// stage memory.  It is gemm_nt_duo's producer epilogue, expression for expression: passes of 16 rows x 64 columns through a
+// stage memory.  Its arithmetic is gemm_nt_duo's producer pass, the same functions (pair_pass_*, hgr_gemm_common.h): passes of 16 rows x 64 columns through a
 // wave-private LDS slice, a lane then owns 8 consecutive columns of a row (8 lanes per row, 8 rows per instruction), 16-byte accesses
 // on xh, 8-byte ones on xl over whole lines, the old pair requested two passes ahead.  A wave's 128 columns are two whole statistic
 // slots (n tiles 0-3 and 4-7); inside a slot the values are paired exactly as in gemm_nt_duo, where a wave's 64 columns are one slot.
@@ -54,9 +54,7 @@ __global__ __launch_bounds__(WD_NT) void gemm_nt_res_wide(GemmArgs p) {
     // tile id = row tile * tiles_n + column tile; every XCD (blocks b, b + 8, ... share an L2) owns a contiguous range of ids, column
     // tiles fastest: the column tiles of a row panel sit on one L2.  grid = number of tiles.
     const int ntiles = p.tiles_m * p.tiles_n, orig = blockIdx.x;
-    const int xcd = orig & 7, q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int xbase = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int tile = xbase + (orig >> 3);
+    const int tile = xcd_first_tile(ntiles, orig & 7) + (orig >> 3);
     if (tile >= ntiles) return;
     const int tm = tile / p.tiles_n;
     const int m0 = tm * WD_BM, n0 = (tile - tm * p.tiles_n) * WD_BN;
@@ -72,12 +70,12 @@ __global__ __launch_bounds__(WD_NT) void gemm_nt_res_wide(GemmArgs p) {
     auto issueA = [&](int t) {
         char *dst = ldsw + (t & 1) * WD_STAGE + WD_PA;
 #pragma unroll
-        for (int i = 0; i < 5; ++i) dma16(rA, At, laneA, t * 128 + i * stepA, dst + i * 8192);
+        for (int i = 0; i < 5; ++i) dma16(rA, laneA, t * 128 + i * stepA, dst + i * 8192);
     };
     auto issueW = [&](int half, int t) {
         char *dst = ldsw + (t & 1) * WD_STAGE + (half ? WD_PW1 : WD_PW0);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dma16(rW, Wt, laneW, t * 128 + i * stepW + half * w1off, dst + i * 8192);
+        for (int i = 0; i < 2; ++i) dma16(rW, laneW, t * 128 + i * stepW + half * w1off, dst + i * 8192);
     };
 
     const int nk = p.K / 64;    // even, >= 4 (host)
@@ -98,49 +96,10 @@ __global__ __launch_bounds__(WD_NT) void gemm_nt_res_wide(GemmArgs p) {
     HGR_RWAIT(9);               // PA(0), PW0(0) landed: my 9 youngest are PW1(0) x2, PA(1) x5, PW0(1) x2
     if (wn) HGR_MBAR();         // ping-pong: group 1 runs one barrier interval behind group 0
 
-    // MODE 0: steady state (t + 2 < nk), 1: second-last K-tile, 2: last K-tile
+    // the shared K-tile (pingpong_ktile, hgr_gemm_common.h) with five m tiles: ph1 issues PW1(t+1), ph2 PA(t+2) and PW0(t+2)
     auto ktile = [&](int t, auto mode_tag) {
-        constexpr int MODE = decltype(mode_tag)::value;
-        const char *st = smem + (t & 1) * WD_STAGE;
-        // ---- ph1: all 80 rows of the wave x its columns 0-63 ----
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            wf[j][0] = *(const vec8 *)(st + WD_PW0 + offW + j * 2048 + sw0);
-            wf[j][1] = *(const vec8 *)(st + WD_PW0 + offW + j * 2048 + sw1);
-        }
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            af[i][0] = *(const vec8 *)(st + WD_PA + offA + i * 2048 + sw0);
-            af[i][1] = *(const vec8 *)(st + WD_PA + offA + i * 2048 + sw1);
-        }
-        if (MODE <= 1) issueW(1, t + 1);                        // behind the reads; its slot was last read in ph2(t - 1), two barriers ago
-        if (MODE <= 1) HGR_RWAIT(9); else HGR_RWAIT(0);         // PW1(t) landed
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = T16<DT>::mfma16(wf[j][kk], af[i][kk], acc[i][j]);
-        __builtin_amdgcn_s_setprio(0);
-        HGR_MBAR();
-        // ---- ph2: columns 64-127, the A fragments stay ----
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            wf[j][0] = *(const vec8 *)(st + WD_PW1 + offW + j * 2048 + sw0);
-            wf[j][1] = *(const vec8 *)(st + WD_PW1 + offW + j * 2048 + sw1);
-        }
-        if (MODE == 0) { issueA(t + 2); issueW(0, t + 2); }     // read in ph1(t), two barriers ago
-        if (MODE == 0) HGR_RWAIT(9); else if (MODE == 1) HGR_RWAIT(2); else HGR_RBAR();      // PA(t+1), PW0(t+1) landed
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][4 + j] = T16<DT>::mfma16(wf[j][kk], af[i][kk], acc[i][4 + j]);
-        __builtin_amdgcn_s_setprio(0);
-        HGR_MBAR();
+        pingpong_ktile<DT, 5, decltype(mode_tag)::value, WD_PA, WD_PW0, WD_PW1>(smem + (t & 1) * WD_STAGE, offA, offW, sw0, sw1, acc, wf, af,
+            [&]() { issueW(1, t + 1); }, [&]() { issueA(t + 2); issueW(0, t + 2); });
     };
     for (int t = 0; t < nk - 2; ++t) ktile(t, std::integral_constant<int, 0>());
     ktile(nk - 2, std::integral_constant<int, 1>());
@@ -198,33 +157,15 @@ __global__ __launch_bounds__(WD_NT) void gemm_nt_res_wide(GemmArgs p) {
             const vec8 oh = __builtin_bit_cast(vec8, ohb[pb][q]);
             const u32x2 ol = olb[pb][q];
             float v[8];
-            // (acc + bias) + old x (pair_dec4: hi's bits + the low byte's 8 mantissa bits)
-            v[0] = (lo4[0] + b8lo[0]) + pair_dec4<DT, 0>(oh[0], ol[0]); v[1] = (lo4[1] + b8lo[1]) + pair_dec4<DT, 1>(oh[1], ol[0]);
-            v[2] = (lo4[2] + b8lo[2]) + pair_dec4<DT, 2>(oh[2], ol[0]); v[3] = (lo4[3] + b8lo[3]) + pair_dec4<DT, 3>(oh[3], ol[0]);
-            v[4] = (hi4[0] + b8hi[0]) + pair_dec4<DT, 0>(oh[4], ol[1]); v[5] = (hi4[1] + b8hi[1]) + pair_dec4<DT, 1>(oh[5], ol[1]);
-            v[6] = (hi4[2] + b8hi[2]) + pair_dec4<DT, 2>(oh[6], ol[1]); v[7] = (hi4[3] + b8hi[3]) + pair_dec4<DT, 3>(oh[7], ol[1]);
+            pair_pass_values<DT>(lo4, hi4, b8lo, b8hi, oh, ol, v);
             u32x4 nh;
             u32x2 nl;
-            {
-                unsigned tq[8];
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) nh[e2] = pair_split2<DT>(v[2 * e2], v[2 * e2 + 1], tq[2 * e2], tq[2 * e2 + 1]);
-                unsigned q0, q1;
-                pair_put_q<DT, 0>(q0, tq[0]); pair_put_q<DT, 1>(q0, tq[1]); pair_put_q<DT, 2>(q0, tq[2]); pair_put_q<DT, 3>(q0, tq[3]);
-                pair_put_q<DT, 0>(q1, tq[4]); pair_put_q<DT, 1>(q1, tq[5]); pair_put_q<DT, 2>(q1, tq[6]); pair_put_q<DT, 3>(q1, tq[7]);
-                nl = (u32x2){q0, q1};
-            }
+            pair_pass_split<DT>(v, nh, nl);
             *(u32x4 *)(hw0 + h * 128 + (xo + (rl + q * 8) * ldxB)) = nh;
             *(u32x2 *)(lw0 + h * 64 + (lo8 + (rl + q * 8) * ldlB)) = nl;
-            s1[q] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-            s2[q] = (__builtin_fmaf(v[0], v[0], v[1] * v[1]) + __builtin_fmaf(v[2], v[2], v[3] * v[3])) +
-                    (__builtin_fmaf(v[4], v[4], v[5] * v[5]) + __builtin_fmaf(v[6], v[6], v[7] * v[7]));
+            pair_pass_sums(v, s1[q], s2[q]);
         }
-#define HGR_DPP_STAGE8(CTRL) _Pragma("unroll") for (int q = 0; q < 2; ++q) { \
-            s1[q] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s1[q]), CTRL, 0xF, 0xF, true)); \
-            s2[q] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s2[q]), CTRL, 0xF, 0xF, true)); }
-        HGR_DPP_STAGE8(0xB1) HGR_DPP_STAGE8(0x4E) HGR_DPP_STAGE8(0x141)
-#undef HGR_DPP_STAGE8
+        pair_pass_reduce(s1, s2);
         if (c8 == 0) {
 #pragma unroll
             for (int q = 0; q < 2; ++q) {

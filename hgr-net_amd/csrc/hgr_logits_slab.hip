@@ -81,13 +81,13 @@ __global__ __launch_bounds__(LS_NT) void logits_slab(SlabArgs p) {
         if (HGR_LAB_ON(p.dbg & 2)) return;
         char *dst = ldsw + (t & 1) * LS_STAGE + piece;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dma16(rA, p.A, off[i], t * 128, dst + i * 8192);
+        for (int i = 0; i < 4; ++i) dma16(rA, off[i], t * 128, dst + i * 8192);
     };
     auto issueW = [&](int t) {
         if (HGR_LAB_ON(p.dbg & 4)) return;
         char *dst = ldsw + (t & 1) * LS_STAGE + LS_PW;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dma16(rW, p.W, oW[i], t * 128, dst + i * 8192);
+        for (int i = 0; i < 2; ++i) dma16(rW, oW[i], t * 128, dst + i * 8192);
     };
 
     f32x4 acc[4][6];            // [m tile][n tile]: logits[m0 + 64 wave + 16 i + r][n0 + 16 j + 4 g .. + 3]

@@ -95,12 +95,12 @@ __global__ __launch_bounds__(PE_NT) void vit_patch_embed_ln(const float *__restr
         const int ts = min(t, PE_NK - 1);                       // (behind the last K-tile: see the loop)
         const int soff = (ts >> 5) * RR4 + (ts & 31) * R4;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dma16(rA, abase, oA[i], soff, dst + i * 8192);
+        for (int i = 0; i < 2; ++i) dma16(rA, oA[i], soff, dst + i * 8192);
     };
     auto issueW = [&](int half, int t) {                      // half 0 = piece W0, 1 = W1
         char *dst = ldsw + (half ? PE_W1 : PE_W0) + (t & 1) * PE_WSZ;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) dma16(rW, conv_w, oW[i], min(t, PE_NK - 1) * 64 + half * (48 * PE_K * 2), dst + i * 8192);
+        for (int i = 0; i < 3; ++i) dma16(rW, oW[i], min(t, PE_NK - 1) * 64 + half * (48 * PE_K * 2), dst + i * 8192);
     };
 
     // fragment addresses (see the LDS images above)

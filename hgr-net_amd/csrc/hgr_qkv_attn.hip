@@ -48,25 +48,16 @@ typedef __attribute__((ext_vector_type(8))) short qa_s16x8;
 
 // a phase's LDS-DMAs are issued BEHIND its fragment reads (as in gemm_nt_duo): an LDS-DMA instruction can stall at the CU's one
 // vector-memory address path, and in front of the reads that stall delayed the reads, the wait and the MFMA burst behind them.  Three
-// interleaved pairs, one box: 110.1 -> 107.9 us per launch, bit-identical.  -DHGR_QA_ISSUE_LATE=0: the round-4 order
-#ifndef HGR_QA_VASM
-#define HGR_QA_VASM 1
-#endif
-// Experiment, OFF (-DHGR_QA_STATS_DMA=1 builds it): the tile's raw slot statistics staged by LDS-DMA into the V region (unused while the
-// main loop runs) during the second-last K-tile - the six DMAs per wave (waves 0-3) ride in the in-order vmcnt stream of the main loop,
-// the two counted waits of that K-tile allow for them, the last K-tile's vmcnt(0) completes them - instead of a dependent global round
-// trip between the main loop and the q / k / v conversion.  Measured twice in round 6 (tools/qa_stamps.py + three interleaved rounds of
+// interleaved pairs, one box: 110.1 -> 107.9 us per launch, bit-identical.
+// Measured and not kept: the tile's raw slot statistics staged by LDS-DMA into the V region (unused while the main loop runs) during the
+// second-last K-tile - the six DMAs per wave (waves 0-3) ride in the in-order vmcnt stream of the main loop, the two counted waits of
+// that K-tile allow for them, the last K-tile's vmcnt(0) completes them - instead of a dependent global round trip between the main
+// loop and the q / k / v conversion.  Measured twice in round 6 (tools/qa_stamps.py + three interleaved rounds of
 // the image tower each): (a) issued behind the seam barrier: statistics section 1 880 -> 1 160 ticks of a 37 400-tick tile, launch
 // 107.6 -> 108.6 us, tower 4.78 -> 4.81 ms; (b) issued mid-loop as built here: section 1 880 -> 1 160 again, main loop 23 050 -> 24 000,
 // tile 37 364 -> 37 664, tower 4.78 -> 4.80 ms.  The round trip is real (5 % of a tile) but whatever removes it gives the time back
 // elsewhere; round 4 found the same with a third placement.  Under the package power limit idle cycles are not free
 // time to be harvested: the clock drops when they are filled.
-#ifndef HGR_QA_STATS_DMA
-#define HGR_QA_STATS_DMA 0
-#endif
-#ifndef HGR_QA_ISSUE_LATE
-#define HGR_QA_ISSUE_LATE 1
-#endif
 constexpr int QA_NT = 512;
 constexpr int QA_STAGE = 57344;                              // PA0 16 K | PA1 16 K | PW 24 K
 constexpr int QA_PA0 = 0, QA_PA1 = 16384, QA_PW = 32768;
@@ -74,7 +65,6 @@ constexpr int QA_PA0 = 0, QA_PA1 = 16384, QA_PW = 32768;
 constexpr int QA_VR = 72;
 constexpr int QA_Q = QA_STAGE, QA_K = QA_Q + 32768, QA_V = QA_K + 32768, QA_LN = QA_V + 256 * QA_VR * 2;
 constexpr int QA_LDS = QA_LN + 2048;                         // 161 792 B of the CU's 163 840
-constexpr int QA_ST = QA_V;                                  // staged slot statistics [q < 8][256 rows] x 16 B = 32 KB of V's 36 KB (HGR_QA_STATS_DMA)
 
 #ifdef HGR_LAB
 // lab builds only: s_memtime stamps of wave 0 around the sections of the workgroup's SECOND tile (steady state), read back through
@@ -107,13 +97,13 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
     // p.hsplit == 2: XCD x owns the head half x & 1 of the row tiles of quarter x >> 1 - its L2 then holds HALF of the folded weights
     // (1.8 MB at 12 heads) beside the row panels in flight, instead of re-reading all of them in every round of tiles.
     const int ntiles = p.tiles_m * p.H, orig = blockIdx.x, G = gridDim.x;
-    const int xcd = orig & 7, q8 = ntiles >> 3, r8 = ntiles & 7;
+    const int xcd = orig & 7;
     const bool split = p.hsplit == 2;
     const int mlo = split ? (xcd >> 1) * p.tiles_m / 4 : 0;
     const int HS = split ? p.H >> 1 : p.H, hbase = split ? (xcd & 1) * HS : 0;
-    const int xbase = split ? 0 : xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    const int xcnt = split ? (((xcd >> 1) + 1) * p.tiles_m / 4 - mlo) * HS : q8 + (xcd < r8 ? 1 : 0);
-    const int xwgs = (G >> 3) + (xcd < (G & 7) ? 1 : 0);
+    const int xbase = split ? 0 : xcd_first_tile(ntiles, xcd);
+    const int xcnt = split ? (((xcd >> 1) + 1) * p.tiles_m / 4 - mlo) * HS : xcd_tile_count(ntiles, xcd);
+    const int xwgs = xcd_tile_count(G, xcd);
     int cur = orig >> 3;                                     // index of this workgroup's tile inside the XCD's range
     if (cur >= xcnt) return;
     const int rows_valid = p.S * p.L;
@@ -147,25 +137,12 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
     auto issueA = [&](const unsigned (&off)[2], int piece, int t) {
         char *dst = ldsw + (t & 1) * QA_STAGE + piece;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dma16(rA, p.A, off[i], t * 128, dst + i * 8192);
+        for (int i = 0; i < 2; ++i) dma16(rA, off[i], t * 128, dst + i * 8192);
     };
     auto issueW = [&](int t) {
         char *dst = ldsw + (t & 1) * QA_STAGE + QA_PW;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) dma16(rW, p.W, oW[i], t * 128, dst + i * 8192);
-    };
-    // Slot statistics of the tile at m0 (waves 0-3: row 64 wave + lane, entry q = slots 2 q, 2 q + 1) -> LDS [q][row], issued at the top
-    // of the second-last K-tile; read back by the wave that issued it (thread t: row t).
-    const int nq = p.ln_slots >> 1;
-    const bool st_dma = HGR_QA_STATS_DMA && !(p.ln_slots & 1) && (nq == 2 || nq == 4 || nq == 5 || nq == 6 || nq == 8);
-    const __amdgpu_buffer_rsrc_t rS = dma_rsrc(p.ln_stats);
-    auto issueStats = [&]() {
-        if (!st_dma || wave >= 4) return;
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const unsigned so = (unsigned)min(m0 + wave * 64 + ln, p.M - 1) * (unsigned)(p.ln_slots * 8);
-        char *dst = smem + QA_ST + wave * 1024;
-        for (int q = 0; q < nq; ++q) dma16(rS, (const char *)p.ln_stats, so, q * 16, dst + q * 4096);
+        for (int i = 0; i < 3; ++i) dma16(rW, oW[i], t * 128, dst + i * 8192);
     };
 
     const int nk = p.K / 64;    // >= 2 (host guarantees)
@@ -200,11 +177,7 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
     auto ktile = [&](int t, auto mode_tag) {
         constexpr int MODE = decltype(mode_tag)::value;
         const char *st = smem + (t & 1) * QA_STAGE;
-        if (MODE == 1) issueStats();          // m0 is still this tile's (set_tile for the next one runs in the epilogue); V is free: the seam barrier is behind us
         // ---- ph1: rows 0-31 of the wave x all 96 columns ----
-#if !HGR_QA_ISSUE_LATE
-        if (MODE <= 1) issueA(oA1, QA_PA1, t + 1);              // its slot was last read in ph2(t - 1), two barriers ago
-#endif
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
             wf[j][0] = *(const vec8 *)(st + QA_PW + offW + j * 2048 + sw0);
@@ -215,12 +188,8 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
             af[i][0] = *(const vec8 *)(st + QA_PA0 + offA + i * 2048 + sw0);
             af[i][1] = *(const vec8 *)(st + QA_PA0 + offA + i * 2048 + sw1);
         }
-#if HGR_QA_ISSUE_LATE
-        if (MODE <= 1) issueA(oA1, QA_PA1, t + 1);
-#endif
-        if (MODE == 1 && st_dma && wave < 4) {                  // + this wave's nq statistics DMAs, issued at the top of this K-tile
-            switch (nq) { case 2: HGR_RWAIT(9); break; case 4: HGR_RWAIT(11); break; case 5: HGR_RWAIT(12); break; case 6: HGR_RWAIT(13); break; default: HGR_RWAIT(15); }
-        } else if (MODE <= 1) HGR_RWAIT(7); else HGR_RWAIT(0);  // PA1(t) landed
+        if (MODE <= 1) issueA(oA1, QA_PA1, t + 1);              // its slot was last read in ph2(t - 1), two barriers ago
+        if (MODE <= 1) HGR_RWAIT(7); else HGR_RWAIT(0);         // PA1(t) landed
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -231,20 +200,13 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
         __builtin_amdgcn_s_setprio(0);
         HGR_MBAR();
         // ---- ph2: rows 32-63 ----
-#if !HGR_QA_ISSUE_LATE
-        if (MODE == 0) { issueA(oA0, QA_PA0, t + 2); issueW(t + 2); }     // read in ph1(t), two barriers ago
-#endif
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             af[i][0] = *(const vec8 *)(st + QA_PA1 + offA + i * 2048 + sw0);
             af[i][1] = *(const vec8 *)(st + QA_PA1 + offA + i * 2048 + sw1);
         }
-#if HGR_QA_ISSUE_LATE
-        if (MODE == 0) { issueA(oA0, QA_PA0, t + 2); issueW(t + 2); }
-#endif
-        if (MODE == 1 && st_dma && wave < 4) {
-            switch (nq) { case 2: HGR_RWAIT(4); break; case 4: HGR_RWAIT(6); break; case 5: HGR_RWAIT(7); break; case 6: HGR_RWAIT(8); break; default: HGR_RWAIT(10); }
-        } else if (MODE == 0) HGR_RWAIT(7); else if (MODE == 1) HGR_RWAIT(2); else HGR_RBAR();      // PA0(t+1), PW(t+1) landed
+        if (MODE == 0) { issueA(oA0, QA_PA0, t + 2); issueW(t + 2); }     // read in ph1(t), two barriers ago
+        if (MODE == 0) HGR_RWAIT(7); else if (MODE == 1) HGR_RWAIT(2); else HGR_RBAR();      // PA0(t+1), PW(t+1) landed
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -289,42 +251,8 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
     asm volatile("" : "+v"(tid_e));
     if (tid_e < 256) {
         const f32x4 *sp = (const f32x4 *)(p.ln_stats + (int64_t)min(m0c + tid_e, p.M - 1) * p.ln_slots * 2);
-        float s1 = 0.f, s2 = 0.f;
-        if (st_dma) {
-            // four entries at a time, summed in slot order like the loads of the other path (entries >= nq are whatever V held: read,
-            // never summed); inline asm: an LDS read the compiler can see is ordered behind every LDS-DMA in flight
-            const unsigned sa = (unsigned)(uintptr_t)(AS3 char *)(smem + QA_ST) + (unsigned)tid_e * 16u;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x4 tl[4];
-                if (h == 0) asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:4096\n\tds_read_b128 %2, %4 offset:8192\n\tds_read_b128 %3, %4 offset:12288\n\ts_waitcnt lgkmcnt(0)"
-                                         : "=&v"(tl[0]), "=&v"(tl[1]), "=&v"(tl[2]), "=&v"(tl[3]) : "v"(sa) : "memory");
-                else asm volatile("ds_read_b128 %0, %4 offset:16384\n\tds_read_b128 %1, %4 offset:20480\n\tds_read_b128 %2, %4 offset:24576\n\tds_read_b128 %3, %4 offset:28672\n\ts_waitcnt lgkmcnt(0)"
-                                  : "=&v"(tl[0]), "=&v"(tl[1]), "=&v"(tl[2]), "=&v"(tl[3]) : "v"(sa) : "memory");
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (h * 4 + i < nq) { s1 += tl[i][0] + tl[i][2]; s2 += tl[i][1] + tl[i][3]; }
-                if (nq <= 4) break;
-            }
-        } else {
-        auto fixed = [&](auto nq_tag) {
-            constexpr int NQ = decltype(nq_tag)::value;
-            f32x4 t[NQ];
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) t[i] = sp[i];
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) { s1 += t[i][0] + t[i][2]; s2 += t[i][1] + t[i][3]; }
-        };
-        switch (p.ln_slots) {
-            case 4: fixed(std::integral_constant<int, 2>()); break;
-            case 8: fixed(std::integral_constant<int, 4>()); break;
-            case 10: fixed(std::integral_constant<int, 5>()); break;
-            case 12: fixed(std::integral_constant<int, 6>()); break;
-            case 16: fixed(std::integral_constant<int, 8>()); break;
-            default:
-                for (int i = 0; i < p.ln_slots / 2; ++i) { const f32x4 t = sp[i]; s1 += t[0] + t[2]; s2 += t[1] + t[3]; }
-        }
-        }
+        float s1, s2;
+        ln_row_sums(sp, p.ln_slots, s1, s2);
         const float2 mr = ln_finalize(s1, s2, 1.0f / (float)p.K, p.ln_eps);
         const qa_f2 mv = {mr.x, mr.y};
         asm volatile("ds_write_b64 %0, %1" ::"v"(lnrow_a + tid_e * 8), "v"(mv) : "memory");
@@ -422,7 +350,6 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
 #pragma unroll
             for (int ks = 0; ks < KT; ++ks) {
                 const int v0 = min(kb + ks * 32 + g * 4 + (r >> 2), 255), v1 = min(kb + ks * 32 + 16 + g * 4 + (r >> 2), 255);
-#if HGR_QA_VASM
                 // as inline asm: hipcc puts s_waitcnt vmcnt(0) in front of a transposing read it can see while LDS-DMAs are pending (the
                 // next tile's first K-tile, requested above, lands in stage 0 - never in V) - here that is also a wait for the previous
                 // unit's output stores.  The reads are waited for by hand in front of the P V products (QA_V_WAIT).
@@ -431,13 +358,6 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
                              : "=&v"(vlo[ks][0]), "=&v"(vlo[ks][1]), "=&v"(vlo[ks][2]), "=&v"(vlo[ks][3]) : "v"(a0));
                 asm volatile("ds_read_b64_tr_b16 %0, %4\n\tds_read_b64_tr_b16 %1, %4 offset:32\n\tds_read_b64_tr_b16 %2, %4 offset:64\n\tds_read_b64_tr_b16 %3, %4 offset:96"
                              : "=&v"(vhi[ks][0]), "=&v"(vhi[ks][1]), "=&v"(vhi[ks][2]), "=&v"(vhi[ks][3]) : "v"(a1));
-#else
-#pragma unroll
-                for (int td = 0; td < 4; ++td) {
-                    vlo[ks][td] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3 qa_s16x4 *)(ldsV + (v0 * QA_VR + td * 16 + (r & 3) * 4) * 2));
-                    vhi[ks][td] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3 qa_s16x4 *)(ldsV + (v1 * QA_VR + td * 16 + (r & 3) * 4) * 2));
-                }
-#endif
             }
             f32x4 sc[2 * KT];
 #pragma unroll
@@ -471,12 +391,10 @@ __global__ __launch_bounds__(QA_NT) void qkv_attn(QkvAttnArgs p) {
             f32x4 o[4];
 #pragma unroll
             for (int td = 0; td < 4; ++td) o[td] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#if HGR_QA_VASM
             // every V^T fragment has landed (they were issued before the softmax); the registers pass through the statement so that no
             // product can be scheduled in front of it
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vlo[0][0]), "+v"(vlo[0][1]), "+v"(vlo[0][2]), "+v"(vlo[0][3]), "+v"(vhi[0][0]), "+v"(vhi[0][1]), "+v"(vhi[0][2]), "+v"(vhi[0][3]),
                                                   "+v"(vlo[1][0]), "+v"(vlo[1][1]), "+v"(vlo[1][2]), "+v"(vlo[1][3]), "+v"(vhi[1][0]), "+v"(vhi[1][1]), "+v"(vhi[1][2]), "+v"(vhi[1][3]));
-#endif
 #pragma unroll
             for (int ks = 0; ks < KT; ++ks) {
                 vec8 pf;

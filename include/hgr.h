@@ -11,7 +11,7 @@
  *   - plain pointers and sizes only; every tensor argument is a raw DEVICE pointer, row-major;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); every call is asynchronous
  *     and stream-ordered, never synchronises and allocates no device memory.  The only process-wide mutable state is
- *     (a) the development knobs hgr_gemm_set_tile / hgr_gemm_set_tail / hgr_gemm_set_persist / hgr_gemm_set_ws / hgr_gemm_set_p8 (plan
+ *     (a) the development knobs hgr_gemm_set_tile / hgr_gemm_set_tail / hgr_gemm_set_persist / hgr_gemm_set_p8 (plan
  *         overrides for A/B runs and tests; hgr_gemm_plan_capture arms the CALLING THREAD only) and
  *     (b) the optional RCCL communicator created / destroyed explicitly by hgr_comm_init / hgr_comm_destroy and
      (c) the 16-slot scratch ring of hgr_sumsq (see there);
@@ -97,20 +97,6 @@ int hgr_gemm_set_tail(int enabled, int full_panels);
  * Returns the previous setting.
  */
 int hgr_gemm_set_persist(int enabled);
-
-/*
- * Role-split form of the tower GEMMs (round 5 EXPERIMENT; csrc/hgr_gemm_ws.hip): launches of hgr_gemm_nt (16-bit output, epilogues NONE /
- * BIAS / BIAS_RELU), hgr_gemm_nt_ln and hgr_gemm_nt_res_stats* that are made of whole 256 x 128 tiles (M % 256 == 0, N % 128 == 0,
- * K % 128 == 0, K >= 768, at least one tile per CU) run as ONE persistent workgroup per CU of four matrix waves (LDS fragment reads
- * + MFMA only, fragments prefetched a phase ahead) and four helper waves that issue the operand LDS-DMAs and run the epilogue of tile
- * i - nn.Linear's bias, QuickGELU (clip/model.py:162-164), the folded LayerNorm (clip/model.py:153-159), the residual add of
- * clip/model.py:186-187 - under the MFMAs of tile i + 1.  Same tiles, same K order, same epilogue arithmetic as the
- * two-workgroups-per-CU kernel: results are bit-identical (tests/test_gpu_kernels.py::test_gemm_ws_equals_duo).  It does NOT beat
- * that kernel (the epilogue's vector instructions take the same issue slots from the SIMD's matrix wave whichever wave runs them;
- * both forms are bound by LDS bandwidth - DESIGN.md 4.1, profiles/NOTES.md round 5), so enabled = 0 is the default (HGR_WS=1 / this
- * call switch it on: A/B runs, tests).  Process-wide development knob like hgr_gemm_set_tile.  Returns the previous setting.
- */
-int hgr_gemm_set_ws(int enabled);
 
 /*
  * The LayerNorm-folded consumer GEMM (hgr_gemm_nt_ln) also exists as ONE persistent 512-thread workgroup per CU on 256 x 256 tiles
@@ -542,12 +528,12 @@ int hgr_gemm_tn_tile(int Na, int Nb);
  * hgr_gemm_plan_capture(NULL, 0) disarms without a call and returns 1 if the thread was still armed, 0 if not.  Host
  * only - the operands are never dereferenced, so tests replay shapes without a device (tests/golden/gemm_plans.json).
  *   kernel   HGR_KERNEL_*;  variant: gemm_nt_128 0 plain / 1 tall 256 x 64 / 2 conv / 3 conv tall; gemm_nt_256 1 = conv; gemm_nt_duo
- *            0 plain / 1 residual producer / 2 LayerNorm consumer / 4 dual output / 5 conv; gemm_nt_ws 0 plain / 1 consumer / 2 producer;
+ *            0 plain / 1 residual producer / 2 LayerNorm consumer / 4 dual output / 5 conv;
  *            conv-direct: the input channels
- *   epilogue, out_f32, act   the instantiation (act: QuickGELU 1 / ReLU 2 of gemm_nt_ws and gemm_nt_p8, relu of conv-direct)
+ *   epilogue, out_f32, act   the instantiation (act: QuickGELU 1 of gemm_nt_p8, relu of conv-direct)
  *   grid_x, grid_y           the launch grid (0 for conv-direct, which sizes its own)
  *   tiles_m .. vec_ok        the plan as the kernel receives it;  row0, rows: the rows of A / C the launch covers */
-enum { HGR_KERNEL_128 = 1, HGR_KERNEL_256 = 2, HGR_KERNEL_DUO = 3, HGR_KERNEL_WS = 4, HGR_KERNEL_P8 = 5, HGR_KERNEL_CONV_DIRECT = 6 };
+enum { HGR_KERNEL_128 = 1, HGR_KERNEL_256 = 2, HGR_KERNEL_DUO = 3, HGR_KERNEL_P8 = 5, HGR_KERNEL_CONV_DIRECT = 6 };   /* 4: unused (a retired kernel) */
 typedef struct { int32_t kernel, variant, epilogue, out_f32, act, grid_x, grid_y, tiles_m, tiles_n, total,
                  nbig, big_panels, tiles_m_half, group, m_fastest, vec_ok, row0, rows; } hgr_gemm_launch;
 int hgr_gemm_plan_capture(hgr_gemm_launch *out, int max_launches);

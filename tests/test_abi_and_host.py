@@ -32,9 +32,9 @@ def test_gemm_plans_match_golden(tmp_path, golden_dir):
     """Which kernel, tile plan and grid every route of the NT GEMM family takes (hgr_gemm_plan_capture: validated and planned, nothing
     launched, no device needed) against tests/golden/gemm_plans.json.  The table was recorded from the host code BEFORE the plan step
     existed - a scratch build of that commit with a tagged print in front of every launch_* call of hgr_gemm.hip and of the post-adjustment
-    grid / total inside launch_duo, launch_ws and launch_p8, run on a machine without a GPU (256 CUs assumed, as on an MI355X) - so it
+    grid / total inside launch_duo and launch_p8, run on a machine without a GPU (256 CUs assumed, as on an MI355X) - so it
     pins the routes the GPU parity tests name in their docstrings: the shapes of test_gemm_tail_plan_is_bit_identical,
-    test_gemm_res_stats_persistent_is_bit_identical, test_gemm_ws_equals_duo and test_gemm_p8_equals_duo under their switches, the
+    test_gemm_res_stats_persistent_is_bit_identical and test_gemm_p8_equals_duo under their switches, the
     ViT-B/32 batch-512 tower launches, the corners of the tail plan and of the cost model, split-K and every branch of the convolution
     ladder.  A changed threshold shows up here instead of silently moving a parity test off the path it was written for.  The library
     reads its environment once, so every environment of the table gets a fresh process, one after another, started without HGR_*
@@ -77,7 +77,7 @@ def test_gemm_plans_match_golden(tmp_path, golden_dir):
 
 
 def test_gemm_32bit_offset_guard_flips_at_4gb():
-    """gemm_nt_duo, gemm_nt_ws, gemm_nt_p8, the LayerNorm forms and hgr_gemm_nt_ln_mha address their operands with 32-bit byte offsets.
+    """gemm_nt_duo, gemm_nt_p8, the LayerNorm forms and hgr_gemm_nt_ln_mha address their operands with 32-bit byte offsets.
     One step below M * lda * 2 = 2^32 (and N * ldw * 2 = 2^32) hgr_gemm_nt plans them, at the limit it falls back to the 128 / 256
     kernels (64-bit pointers); the entry points that have no other kernel reject the call, and ops.ln_mha_ok / ops.gelu_dual_ok say
     the same as the library on both sides.  With the plan capture armed nothing is launched and no operand is read, and a rejected
@@ -87,7 +87,7 @@ def test_gemm_32bit_offset_guard_flips_at_4gb():
     lib = _lib.load()
     p = torch.zeros(64, dtype=torch.float16).data_ptr()
     assert p % 16 == 0
-    small, narrow = (1, 2), (3, 4, 5)                                  # HGR_KERNEL_128 / _256; _DUO / _WS / _P8
+    small, narrow = (1, 2), (3, 5)                                     # HGR_KERNEL_128 / _256; _DUO / _P8
 
     def nt(m, n, k, lda, ldw, epi=EPI_NONE, out32=1):
         return [d["kernel"] for d in ops.gemm_plan(lambda: _lib.call("hgr_gemm_nt", p, lda, p, ldw, p, n, p, p, n, m, n, k, HGR_F16, epi, out32, 0))]
@@ -95,22 +95,19 @@ def test_gemm_32bit_offset_guard_flips_at_4gb():
     def limit(rows):                                                   # the smallest leading dimension with rows * ld * 2 >= 2^32, % 8 == 0
         return -(-(1 << 32) // (2 * rows * 8)) * 8
 
-    prev_tile, prev_ws = ops.gemm_set_tile(0), lib.hgr_gemm_set_ws(0)
+    prev_tile = ops.gemm_set_tile(0)
     try:
-        for tile, ws, (m, n, k), epi, out32, kernel in ((0, 0, (8192, 4096, 128), EPI_NONE, 1, 3),       # gemm_nt_duo by shape
-                                                        (2, 0, (1024, 256, 128), EPI_NONE, 1, 3),        # ... and pinned
-                                                        (0, 1, (4096, 2048, 768), EPI_BIAS, 0, 4)):      # gemm_nt_ws
+        for tile, (m, n, k), epi, out32, kernel in ((0, (8192, 4096, 128), EPI_NONE, 1, 3),       # gemm_nt_duo by shape
+                                                    (2, (1024, 256, 128), EPI_NONE, 1, 3)):       # ... and pinned
             ops.gemm_set_tile(tile)
-            lib.hgr_gemm_set_ws(ws)
             la, lw = limit(m), limit(n)
             assert (m * (la - 8) * 2 < 1 << 32 <= m * la * 2) and (n * (lw - 8) * 2 < 1 << 32 <= n * lw * 2)
             assert nt(m, n, k, la - 8, lw - 8, epi, out32) == [kernel]
             for lda, ldw in ((la, k), (k, lw), (la, lw)):
                 plan = nt(m, n, k, lda, ldw, epi, out32)
-                assert plan and all(kn in small for kn in plan) and not any(kn in narrow for kn in plan), (tile, ws, lda, ldw, plan)
+                assert plan and all(kn in small for kn in plan) and not any(kn in narrow for kn in plan), (tile, lda, ldw, plan)
     finally:
         ops.gemm_set_tile(prev_tile)
-        lib.hgr_gemm_set_ws(prev_ws)
 
     m, n, k = 1024, 256, 128
     la, lw = limit(m), limit(n)
@@ -148,7 +145,7 @@ def test_product_library_has_no_ablation_switches():
     point must not be exported."""
     from hgr_net_amd import _lib
     blob = Path(_lib.__file__).resolve().parent.joinpath("lib", "libhgr.so").read_bytes()
-    for name in (b"HGR_GEMM_DBG", b"HGR_WS_DBG", b"HGR_LS_DBG", b"HGR_LE_DBG"):
+    for name in (b"HGR_GEMM_DBG", b"HGR_LS_DBG", b"HGR_LE_DBG"):
         assert name not in blob, f"{name.decode()} is compiled into libhgr.so"
     assert not hasattr(_lib.load(), "hgr_lab_qa_stamps")
     common = (ROOT / "hgr-net_amd" / "csrc" / "hgr_common.h").read_text()

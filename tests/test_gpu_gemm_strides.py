@@ -19,7 +19,7 @@ from hgr_net_amd._lib import (EPI_ACCUM, EPI_BIAS, EPI_BIAS_ADD16_RELU, EPI_BIAS
 
 DEV = "cuda"
 DTS = [torch.bfloat16, torch.float16]
-K128, K256, DUO, WS, P8 = 1, 2, 3, 4, 5                     # HGR_KERNEL_* of include/hgr.h
+K128, K256, DUO, P8 = 1, 2, 3, 5                           # HGR_KERNEL_* of include/hgr.h
 
 
 def _rand(shape, seed, scale=1.0):
@@ -99,7 +99,7 @@ def _layout_sets(toks):
 
 
 @contextlib.contextmanager
-def _knobs(tile=None, tail=None, ws=None, p8=None):
+def _knobs(tile=None, tail=None, p8=None):
     """Plan knobs for the duration of a case; the previous settings come back whatever happens."""
     lib = _lib.load()
     undo = []
@@ -110,9 +110,6 @@ def _knobs(tile=None, tail=None, ws=None, p8=None):
         if tail is not None:
             prev_t = ops.gemm_set_tail(*tail)
             undo.append(lambda: ops.gemm_set_tail(bool(prev_t)))
-        if ws is not None:
-            prev_w = lib.hgr_gemm_set_ws(ws)
-            undo.append(lambda: lib.hgr_gemm_set_ws(prev_w))
         if p8 is not None:
             prev_p = lib.hgr_gemm_set_p8(p8)
             undo.append(lambda: lib.hgr_gemm_set_p8(prev_p))
@@ -159,8 +156,6 @@ _NT_CASES = {
     "duo_tail": (4252, 4096, 128, dict(tile=2, tail=(True, 15)), [dict(kernel=DUO, variant=0, nbig=480, big_panels=15, tiles_m_half=4)], _ALL, (2,)),
     # all half tiles (few tiles, 128 < M: the class-token tail of a ViT's last block), ragged last half panel
     "duo_half": (500, 256, 256, dict(tile=2), [dict(kernel=DUO, variant=0, nbig=0, big_panels=0, tiles_m_half=4)], _ALL, (2, 50)),
-    # gemm_nt_ws on its smallest covered shape: whole tiles, one per CU, 12 K-tiles
-    "ws": (4096, 2048, 768, dict(ws=1), [dict(kernel=WS, variant=0, tiles_m=16, tiles_n=16, total=256)], ("none16", "bias16", "relu16"), (2,)),
 }
 
 
@@ -251,7 +246,6 @@ def test_gemm_nt_nonlinear_epilogues_strided_bits(dt, case):
 _PRODUCER_CASES = dict(_DUO_CASES)
 # the persistent walk: 690 tiles (510 full + 180 half) on 512 workgroups
 _PRODUCER_CASES["persist"] = (25600, 768, 128, dict(), dict(kernel=DUO, grid_x=512, total=690, nbig=510, big_panels=85, tiles_m_half=30), ())
-_PRODUCER_CASES["ws"] = (4096, 2048, 768, dict(ws=1), dict(kernel=WS, variant=2, tiles_m=16, tiles_n=16, total=256), (2,))
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -289,7 +283,6 @@ def test_gemm_nt_res_stats_strided_bits(dt, case):
 
 _CONSUMER_CASES = dict(_DUO_CASES)
 _CONSUMER_CASES["p8"] = (4096, 4096, 256, dict(p8=1), dict(kernel=P8, tiles_m=16, tiles_n=16, grid_x=256), (2,))
-_CONSUMER_CASES["ws"] = (4096, 2048, 768, dict(ws=1), dict(kernel=WS, variant=1, tiles_m=16, tiles_n=16, total=256), (2,))
 
 
 @pytest.mark.parametrize("dt", DTS)

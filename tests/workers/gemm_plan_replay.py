@@ -35,7 +35,7 @@ ARGTYPES = {
     "hgr_gemm_nt_bias_gelu_dual": [_p, _l, _p, _l, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p],
     "hgr_gemm_nt_qgelu_grad_colsum": [_p, _l, _p, _l, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p],
     "hgr_gemm_plan_capture": [_p, _i],
-    "hgr_gemm_set_tile": [_i], "hgr_gemm_set_tail": [_i, _i], "hgr_gemm_set_persist": [_i], "hgr_gemm_set_ws": [_i], "hgr_gemm_set_p8": [_i],
+    "hgr_gemm_set_tile": [_i], "hgr_gemm_set_tail": [_i, _i], "hgr_gemm_set_persist": [_i], "hgr_gemm_set_p8": [_i],
 }
 
 
@@ -74,7 +74,7 @@ def call(lib, entry, a):
 
 
 def set_knobs(lib, knobs):
-    """Applies {"tile", "tail": [enabled, full_panels], "persist", "ws", "p8"} through the setters; returns what restores them (the
+    """Applies {"tile", "tail": [enabled, full_panels], "persist", "p8"} through the setters; returns what restores them (the
     setters return the previous value; hgr_gemm_set_tail that of `enabled` only, so full_panels goes back to -1 = choose, which is
     what a process that forced no panel count has)."""
     prev = {}

@@ -8,7 +8,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
-from ws_bench import LnC, LnP, timeit
+from gemm_cases import LnC, LnP, timeit
 res = {}
 for name, case in (("fc_lnc_gelu", LnC(25600, 3072, 768, True)), ("proj_lnp", LnP(25600, 768, 3072)), ("out_lnp", LnP(25600, 768, 768))):
     f = lambda: case.run(0)

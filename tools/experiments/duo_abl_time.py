@@ -4,8 +4,7 @@ import sys, json, os
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent.parent))
 import torch
-from tools.ws_bench import LnC, Plain, LnP, timeit, set_ws
-set_ws(0)
+from tools.gemm_cases import LnC, timeit
 M = 25600
 cases = {"fc": LnC(M, 3072, 768, True), "qkv": LnC(M, 2304, 768, False), "big": LnC(M, 3072, 3072, False)}
 for _ in range(3):

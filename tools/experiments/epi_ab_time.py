@@ -5,9 +5,8 @@ import sys, json, os, zlib
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent.parent))
 import torch
-from tools.ws_bench import LnC, Plain, LnP, timeit, set_ws
+from tools.gemm_cases import LnC, Plain, LnP, timeit
 from hgr_net_amd._lib import EPI_NONE
-set_ws(0)
 M = 25600
 cases = {"fc": LnC(M, 3072, 768, True), "qkv": LnC(M, 2304, 768, False), "out": LnP(M, 768, 768), "proj": LnP(M, 768, 3072),
          "patch": Plain(25088, 768, 3072, EPI_NONE)}

@@ -6,7 +6,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent.parent))
 import torch
 from hgr_net_amd import _lib
 from tools.p8_bench import Case
-from tools.ws_bench import timeit
+from tools.gemm_cases import timeit
 _lib.load().hgr_gemm_set_p8(1)
 cases = {"fc": Case(25600, 3072, 768, True), "big": Case(25600, 3072, 3072, False)}
 for _ in range(3):

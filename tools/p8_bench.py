@@ -6,7 +6,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 from hgr_net_amd import ops, _lib
-from tools.ws_bench import LnC, timeit
+from tools.gemm_cases import LnC, timeit
 
 
 def set_p8(on):
