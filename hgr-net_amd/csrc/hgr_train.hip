@@ -1300,6 +1300,9 @@ static int mha_bwd_entry(const char *name, const void *qkv, const void *out, con
                          int B, int L, int heads, int causal, int dtype, void *stream, float *colpart = nullptr) {
     HGR_REQUIRE(qkv && out && dout && dqkv && B >= 1 && heads >= 1, "%s: bad arguments", name);
     HGR_REQUIRE(L >= 1 && L <= 320, "%s: L=%d unsupported (L <= 320)", name, L);
+    HGR_REQUIRE((int64_t)B * heads < (1ll << 31), "%s: grid too large", name);
+    HGR_REQUIRE(hgr_aligned(qkv, 16) && hgr_aligned(out, 16) && hgr_aligned(dout, 16) && hgr_aligned(dqkv, 16),
+                "%s: operands must be 16-byte aligned", name);      // the kernels load vec8
     HGR_REQUIRE(hgr_aligned(stats, 8), "%s: stats must be 8-byte aligned", name);
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "%s: bad dtype %d", name, dtype);
     hipStream_t s = (hipStream_t)stream;

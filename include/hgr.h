@@ -593,7 +593,8 @@ int64_t hgr_layernorm_bwd_scratch_floats(int rows, int W);
 
 /* Attention backward for hgr_mha (L <= 320): dqkv [B*L, 3W] from qkv, the forward output `out` and dout [B*L, W], all
  * 16-bit.  Short sequences (L <= 32) use per-output fp32 loops; longer ones a tiled flash-style kernel on the exact-fp32
- * MFMA that recomputes P from row statistics (nothing L x L is stored). */
+ * MFMA that recomputes P from row statistics (nothing L x L is stored).  These three entry points refuse (HGR_EINVAL, nothing
+ * launched) what hgr_mha refuses: qkv, out, dout or dqkv not 16-byte aligned, and B * heads >= 2^31. */
 int hgr_mha_bwd(const void *qkv, const void *out, const void *dout, void *dqkv, int B, int L, int heads, int causal, int dtype, void *stream);
 /* The same with the row statistics hgr_mha_stats wrote for this qkv (same B, L, heads, causal): identical results, one sweep
  * over the score blocks less.  (L <= 32 runs the single-block kernel, which does not read them.) */

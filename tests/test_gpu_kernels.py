@@ -1104,7 +1104,14 @@ def test_logits_eval_planted_ties_at_group_boundaries(dt):
                                               (3, 64, 2, False),         # L = 64: 4 sequences per tile, every key slot live
                                               (33, 17, 2, True),         # prompts: causal, 15 sequences per tile, query tiles straddle two sequences
                                               (5, 1, 2, False),          # one token per sequence: the softmax of a single score
-                                              (40, 16, 8, True)])        # 16 sequences per tile, no straddling
+                                              (40, 16, 8, True),         # 16 sequences per tile, no straddling
+                                              # the tile-packing edges, S = floor(256 / L) sequences per tile
+                                              (130, 2, 2, True),         # S = 128: a full tile and a 2-sequence one
+                                              (86, 3, 2, False),         # S = 85, one idle row per tile
+                                              (9, 31, 2, True),          # S = 8, 248 rows
+                                              (9, 32, 2, True),          # S = 8, every row live
+                                              (5, 63, 2, False),         # S = 4, 252 rows
+                                              (4, 64, 2, True)])         # causal at the largest L
 def test_gemm_ln_mha_equals_gemm_then_mha(dt, b, l, heads, causal):
     """hgr_gemm_nt_ln_mha (in_proj of the folded ln_1 + scaled dot-product attention in one launch, clip/model.py:171,183-186) must give
     the BITS of hgr_gemm_nt_ln into a qkv buffer followed by hgr_mha, and agree with the fp32 oracle (oracle/clip_ref.mha on the
