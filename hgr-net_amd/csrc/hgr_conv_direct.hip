@@ -330,7 +330,9 @@ int hgr_conv3x3_c32_launch(const void *x, const void *w, const float *bias, void
 }
 
 // out NHWC [B, Ho, Ho, Cout] 16-bit = relu(conv1(image fp32 [B, 3, R, R], stride 2, pad 1) + bias); w [Cout, Kp] 16-bit in
-// (ky, kx, c) order, zero beyond column 27 (the folded layout of clip/model.py `_fold`).
+// (ky, kx, c) order, zero beyond column 27 (the folded layout of clip/model.py `_fold`).  The zeros in columns 27 .. 31 are REQUIRED: the
+// kernel reads columns 0 .. 31 and multiplies 27 .. 31 with a live pixel (tap 0, channel 0), so a nonzero value there changes the result;
+// columns >= 32 are never read.
 extern "C" int hgr_stem_conv1(const float *image, const void *w, const float *bias, void *out, int B, int R, int Cout, int Kp,
                               int dtype, void *stream) {
     HGR_REQUIRE(image && w && bias && out && B >= 1 && R >= 4 && R % 4 == 0 && R <= 1024, "hgr_stem_conv1: bad arguments (R a multiple of 4, <= 1024)");
