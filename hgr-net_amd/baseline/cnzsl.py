@@ -28,26 +28,18 @@ import torch
 from torch import nn
 
 from .. import ops
-from .dgp_eval import MAXL, ListTree, build_list_tree
+from ._shared import K_SLICE, AdamL2State, BufferPool, TreeScorer, mean_rows, metric_string, need_device, sliced_matmul_f32  # noqa: F401
+from .dgp_eval import ListTree, build_list_tree
 
 EPS, MOMENTUM, SCALE = ops.CN_EPS, ops.CN_MOMENTUM, 5.0
-TOP = (1, 2, 5, 10, 20)
+TOP = (1, 2, 5, 10, 20)                        # dgp_eval.TOP: what _shared.TreeScorer and metric_string count
 TRAINABLE = ("model.0.weight", "model.0.bias", "model.2.weight", "model.2.bias", "model.6.weight", "model.6.bias")
 RUNNING = ("model.3.running_mean", "model.3.running_var", "model.5.running_mean", "model.5.running_var")
 
 
-K_SLICE = 512
-
-
 def cosine_logits(xn: torch.Tensor, pn: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-    """out = 25 xn pn^T for row-normalised operands, accumulated over slices of K_SLICE columns.  `hgr_matmul_f32` keeps ONE fp32
-    accumulator per output over the whole inner dimension; at 2048 columns that chain lands 2.3e-6 of max|logit| away from the
-    blocked sum of a CPU BLAS (the reference's fp32 run is 3.9e-7 from fp64), in slices of 512 columns 7.8e-7."""
-    k = xn.shape[1]
-    for j in range(0, k, K_SLICE):
-        e = min(k, j + K_SLICE)
-        ops.matmul_f32(xn[:, j:e], pn[:, j:e].t(), out, alpha=SCALE * SCALE, accumulate=j > 0)
-    return out
+    """out = 25 xn pn^T for row-normalised operands, accumulated over slices of K_SLICE columns (_shared.sliced_matmul_f32)."""
+    return sliced_matmul_f32(xn, pn, out, alpha=SCALE * SCALE)
 
 
 class ClassStandardization(nn.Module):
@@ -79,21 +71,14 @@ class CNZSLModel(nn.Module):
             b = math.sqrt(3.0 / (hid_dim * proto_dim))
             self.model[-2].weight.data.uniform_(-b, b)
         self.to(device)
-        self._bufs = {}
-
-    def _buf(self, key, shape) -> torch.Tensor:
-        b = self._bufs.get(key)
-        if b is None or tuple(b.shape) != tuple(shape) or b.device != self.model[0].weight.device:
-            b = self._bufs[key] = torch.empty(shape, dtype=torch.float32, device=self.model[0].weight.device)
-        return b
+        self._pool = BufferPool(self.model[0].weight)
 
     def running(self):
         m = self.model
         return (m[3].running_mean.data, m[3].running_var.data, m[5].running_mean.data, m[5].running_var.data)
 
     def _check(self, t: torch.Tensor, width: int, what: str) -> torch.Tensor:
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise RuntimeError(f"CNZSLModel needs device tensors ({what}): the product path has no CPU fallback")
+        need_device(t, "CNZSLModel", what)
         if t.dim() != 2 or t.shape[1] != width or t.shape[0] < 1:
             raise ValueError(f"{what} must be [rows, {width}], got {tuple(t.shape)}")
         return t.float().contiguous()
@@ -118,7 +103,7 @@ class CNZSLModel(nn.Module):
     @torch.no_grad()
     def prototypes(self, attrs: torch.Tensor) -> torch.Tensor:
         """`self.model(attrs)` in eval mode: [N, proto_dim], a buffer the next call of this size overwrites."""
-        return self._run(self._check(attrs, self.attr_dim, "attrs"), False, self._buf)["p"]
+        return self._run(self._check(attrs, self.attr_dim, "attrs"), False, self._pool.pool)["p"]
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, attrs: torch.Tensor) -> torch.Tensor:
@@ -126,7 +111,7 @@ class CNZSLModel(nn.Module):
             raise NotImplementedError("training mode: CNZSLModel.forward is inference only (model.eval()); train with CNZSLTrainer")
         x = self._check(x, self.proto_dim, "x")
         p = self.prototypes(attrs)
-        pn, xn = self._buf("pn", p.shape), self._buf("xn", x.shape)
+        pn, xn = self._pool.pool("pn", p.shape), self._pool.pool("xn", x.shape)
         ops.l2norm_rows(p, y32=pn)
         ops.l2norm_rows(x, y32=xn)
         logits = torch.empty((x.shape[0], p.shape[0]), dtype=torch.float32, device=x.device)
@@ -142,16 +127,16 @@ class CNZSLTrainer:
     def __init__(self, model: CNZSLModel, lr: float = 1e-4, weight_decay: float = 1e-4, step_size: int = 25, gamma: float = 0.1,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8):
         self.model, self.lr0, self.wd, self.step_size, self.gamma, self.betas, self.eps = model, lr, weight_decay, int(step_size), gamma, betas, eps
-        self.t = self.epoch = 0
+        self.epoch = 0
         sd = dict(model.named_parameters())
-        self.params = {k: sd[k] for k in TRAINABLE}
-        for k, p in self.params.items():
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                raise ValueError(f"CNZSLTrainer: parameter {k} must be a contiguous fp32 device tensor")
-        self.m = {k: torch.zeros_like(p.data) for k, p in self.params.items()}
-        self.v = {k: torch.zeros_like(p.data) for k, p in self.params.items()}
-        self.g = {k: torch.zeros_like(p.data) for k, p in self.params.items()}
-        self._bufs = {}
+        self.opt = AdamL2State({k: sd[k] for k in TRAINABLE}, betas, eps, weight_decay, "CNZSLTrainer")
+        self.params, self.m, self.v, self.g = self.opt.params, self.opt.m, self.opt.v, self.opt.g
+        self._pool = BufferPool(self.params[TRAINABLE[0]])
+        self._buf = self._pool.pool
+
+    @property
+    def t(self) -> int:
+        return self.opt.t
 
     @property
     def lr(self) -> float:
@@ -159,12 +144,6 @@ class CNZSLTrainer:
 
     def epoch_end(self) -> None:
         self.epoch += 1
-
-    def _buf(self, key, shape) -> torch.Tensor:
-        b = self._bufs.get(key)
-        if b is None or tuple(b.shape) != tuple(shape):
-            b = self._bufs[key] = torch.empty(shape, dtype=torch.float32, device=self.params[TRAINABLE[0]].device)
-        return b
 
     def _scratch(self, rows: int, cols: int) -> torch.Tensor:
         return self._buf("scratch", (max(1, -(-rows // ops.RELU_BWD_CHUNK)) * cols,))
@@ -185,10 +164,7 @@ class CNZSLTrainer:
         logits = cosine_logits(xn, pn, self._buf("logits", (bsz, s)))
         loss_rows, dlogits = self._buf("loss_rows", (bsz,)), self._buf("dlogits", (bsz, s))
         ops.ce_rows(logits, lab, loss_rows, dlogits, gscale=1.0 / bsz)
-        ones = self._bufs.get("ones")
-        if ones is None or ones.numel() != bsz:
-            ones = self._bufs["ones"] = torch.ones(bsz, dtype=torch.float32, device=x.device)
-        loss = ops.dot_f32(loss_rows, ones, self._buf("loss", (1,)), alpha=1.0 / bsz)
+        loss = mean_rows(self._pool, loss_rows, self._buf("loss", (1,)))
         # backward: logits = 25 xn pn^T -> dpn; the row normalisation; ReLU + bias of module 6/7; the chain; ReLU + bias of module 0/1
         g = self.g
         dpn = ops.matmul_f32(dlogits.t(), xn, self._buf("dpn", (s, p)), alpha=SCALE * SCALE)
@@ -223,28 +199,11 @@ class CNZSLTrainer:
     def step(self, feats, labels, attrs_seen) -> torch.Tensor:
         """One iteration of the reference's `train()`; returns the loss as a 0-dim device tensor."""
         loss = self._forward_backward(feats, labels, attrs_seen).clone().reshape(())
-        self.t += 1
-        for k, p in self.params.items():
-            ops.adam_l2(p.data, self.g[k], self.m[k], self.v[k], self.lr, self.t, self.betas, self.eps, self.wd)
+        self.opt.step(self.lr)
         return loss
 
 
 # ---- scoring (cnzsl.py:221-321) ----------------------------------------------------------------------------------------------------------
-def metric_string(acc) -> str:
-    """The string `test()` prints, from the nine counters (hits@1,2,5,10,20, hits_all, path_all, point_all, rows).  The reference
-    keeps the hits and hits_all as fp32 tensors and the other two as Python floats; the divisions are done in those types."""
-    acc = np.asarray(acc, dtype=np.float64)
-    n = int(acc[8])
-    out = "\n"
-    for i, k in enumerate(TOP):
-        out += "Top@{}(%):{:.2f}".format(k, float(np.float32(acc[i]) / np.float32(n) * np.float32(100.0)))
-        out += ", " if k != TOP[-1] else "."
-    out += " hit_ratio(%):{:.2f}".format(float(np.float32(acc[5]) / np.float32(n) * np.float32(100.0)))
-    out += " path_ratio(%):{:.2f}".format(acc[6] / n * 100.0)
-    out += " point_ratio(%):{:.2f}".format(acc[7] / n * 100.0)
-    return out
-
-
 def score_host(logits, targets, tree: ListTree, test_index) -> dict:
     """One batch of `test()` in numpy from its logits [b, >= N]: {'pred' [b, 20] the top-20 test classes, 'top1' [b] the best test
     class, 'lv' [b, n_levels] per depth level the best test class with every off-level column reading -1, 'acc' float64 [9] the
@@ -277,39 +236,21 @@ def score_host(logits, targets, tree: ListTree, test_index) -> dict:
     return {"pred": pred.astype(np.int32), "top1": top1.astype(np.int32), "lv": lv.astype(np.int32), "acc": acc}
 
 
-class CNZSLEvaluator:
+class CNZSLEvaluator(TreeScorer):
     """`test()` on cached features: `nodes` the ordered node list (seen classes first), `test_index` the candidate classes,
     `attrs` [N, A] on the device.  The prototypes of all nodes are computed and normalised once; a batch is one product, one
-    `hgr_eval_rows` launch and the counters, which stay on the device until `result()`."""
+    `hgr_eval_rows` launch and the counters (_shared.TreeScorer: `add`, `add_rows`, `counters`, `result`)."""
 
     def __init__(self, graph_edges, nodes: Sequence[str], test_index, model: CNZSLModel, attrs: torch.Tensor, tree: Optional[ListTree] = None):
-        self.tree = tree if tree is not None else build_list_tree(graph_edges, nodes)
-        n = len(self.tree.nodes)
-        if self.tree.n_levels > MAXL:
-            raise ValueError(f"{self.tree.n_levels} levels: at most {MAXL}")
-        te = np.asarray(test_index.detach().cpu() if torch.is_tensor(test_index) else test_index, dtype=np.int64).reshape(-1)
-        if te.size < max(TOP) or te.min() < 0 or te.max() >= n or np.unique(te).size != te.size:
-            raise ValueError(f"test_index: at least {max(TOP)} distinct node indices below {n}")
-        if attrs.shape[0] != n:
-            raise ValueError(f"attrs has {attrs.shape[0]} rows for {n} nodes")
+        super().__init__(tree if tree is not None else build_list_tree(graph_edges, nodes), test_index, attrs.device)
+        if attrs.shape[0] != self.n:
+            raise ValueError(f"attrs has {attrs.shape[0]} rows for {self.n} nodes")
         was_training = model.training
         p = model.eval().prototypes(attrs)
         model.train(was_training)
-        self.device, self.n, self.k = p.device, n, p.shape[1]
+        self.device, self.k = p.device, p.shape[1]
         self.pn = torch.empty_like(p)
         ops.l2norm_rows(p, y32=self.pn)
-        dev = self.device
-        te32 = torch.tensor(te.astype(np.int32), device=dev)
-        self.index = ops.EvalIndex(torch.from_numpy(self.tree.depth.astype(np.int32)).to(dev), te32, te32, self.tree.n_levels)
-        ptr, anc, lev = [0], [], []
-        for i in range(n):
-            path = self.tree.path(i)
-            anc.extend(path)
-            lev.extend(int(self.tree.depth[q]) for q in path)
-            ptr.append(len(anc))
-        i32 = lambda a: torch.tensor(a, dtype=torch.int32).to(dev)
-        self._ptr_host, self.anc_ptr, self.anc_nodes, self.anc_levels = ptr, i32(ptr), i32(anc), i32(lev)
-        self.acc = torch.zeros(9, dtype=torch.float64, device=dev)
         self._cap, self._buf = 0, None
 
     def logits(self, feats: torch.Tensor) -> torch.Tensor:
@@ -325,33 +266,7 @@ class CNZSLEvaluator:
         ops.l2norm_rows(x, y32=xn)
         return cosine_logits(xn, self.pn, out)
 
-    @torch.no_grad()
-    def add(self, feats: torch.Tensor, target: int):
-        """One batch of ONE class; returns the device outputs (pred [B, 20], top1 [B, 1], lv [B, n_levels])."""
-        t = int(target)
-        if not 0 <= t < self.n:
-            raise ValueError(f"target {target} outside the {self.n} nodes")
-        lv, top1, pred = ops.eval_rows(self.logits(feats), self.index, max(TOP))
-        o, e = self._ptr_host[t], self._ptr_host[t + 1]
-        ops.eval_counters(pred, None, t, top1.view(-1), lv, self.anc_nodes[o:e], self.anc_levels[o:e], self.acc)
-        return pred, top1, lv
-
-    @torch.no_grad()
-    def add_rows(self, feats: torch.Tensor, targets: torch.Tensor):
-        """One batch of MIXED classes: `targets` [B] on the device, node indices."""
-        if not (torch.is_tensor(targets) and targets.is_cuda and targets.numel() == feats.shape[0]):
-            raise ops._lib.HgrError("targets must be a device tensor with one node index per row")
-        tg = targets.to(torch.int64).contiguous().view(-1)
-        lv, top1, pred = ops.eval_rows(self.logits(feats), self.index, max(TOP))
-        ops.eval_counters_rows(pred, tg, top1.view(-1), lv, self.anc_ptr, self.anc_nodes, self.anc_levels, self.acc)
-        return pred, top1, lv
-
-    def counters(self) -> np.ndarray:
-        return self.acc.cpu().numpy()
-
-    def result(self) -> str:
-        """The one host read: the metric string of `test()`."""
-        return metric_string(self.counters())
+    scores = logits
 
 
 # ---- host twins: plain torch, any floating type --------------------------------------------------------------------------------------------

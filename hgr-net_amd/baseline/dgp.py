@@ -23,6 +23,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ._shared import AdamL2State, BufferPool, fmix32, need_device
 
 CHUNK = 256          # edges per work item: bounds the longest gather a single workgroup performs
 
@@ -209,16 +210,6 @@ class GCN_Dense_Att(nn.Module):
 
 
 # ---- training (baseline/DGP/train_gcn_dense_att.py:80-102) -----------------------------------------------------------------
-def _fmix32(h: np.ndarray) -> np.ndarray:
-    """murmur3's 32-bit finaliser on uint64 arrays holding 32-bit values."""
-    m = np.uint64(0xFFFFFFFF)
-    h = h ^ (h >> np.uint64(16))
-    h = (h * np.uint64(0x85EBCA6B)) & m
-    h = h ^ (h >> np.uint64(13))
-    h = (h * np.uint64(0xC2B2AE35)) & m
-    return h ^ (h >> np.uint64(16))
-
-
 def dropout_keep(seed: int, step: int, layer: int, n_rows: int, n_cols: int) -> np.ndarray:
     """Host twin of `hgr_dropout_counter`: the keep mask [n_rows, n_cols] (bool) of training step `step` (1-based) in front of
     layer `layer` (index into `GCN_Dense_Att.layers`).  With 32-bit wrap-around arithmetic and fmix32 = murmur3's finaliser:
@@ -232,10 +223,10 @@ def dropout_keep(seed: int, step: int, layer: int, n_rows: int, n_cols: int) -> 
     if n_rows * n_cols > 0xFFFFFFFF:
         raise ValueError("dropout_keep: n_rows * n_cols must fit the 32-bit element index")
     m = 0xFFFFFFFF
-    key = _fmix32(np.array([((seed & m) + 0x9E3779B9 * ((step + 1) & m)) & m], np.uint64))
-    key = _fmix32(key ^ np.uint64(((layer & m) * 0x85EBCA6B + 0xC2B2AE35) & m))
+    key = fmix32(np.array([((seed & m) + 0x9E3779B9 * ((step + 1) & m)) & m], np.uint64))
+    key = fmix32(key ^ np.uint64(((layer & m) * 0x85EBCA6B + 0xC2B2AE35) & m))
     idx = np.arange(n_rows * n_cols, dtype=np.uint64)
-    return ((_fmix32(idx ^ key) >> np.uint64(31)) != 0).reshape(n_rows, n_cols)
+    return ((fmix32(idx ^ key) >> np.uint64(31)) != 0).reshape(n_rows, n_cols)
 
 
 class DGPTrainer:
@@ -252,25 +243,18 @@ class DGPTrainer:
     def __init__(self, model: GCN_Dense_Att, lr: float = 1e-3, weight_decay: float = 5e-4, seed: int = 0,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8):
         self.model, self.lr, self.wd, self.seed, self.betas, self.eps = model, lr, weight_decay, int(seed), betas, eps
-        self.t = 0                                                  # optimiser steps taken; dropout of step t + 1 uses t + 1
         sides = {k % 2 for k in range(len(model.layers))}
         self.adj = {s: (model.a_op if s == 0 else model.r_op).adjoint() for s in sides}
-        self.params = dict(model.named_parameters())
-        for name, p in self.params.items():
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                raise ValueError(f"DGPTrainer: parameter {name} must be a contiguous fp32 device tensor")
-        self.m = {k: torch.zeros_like(p.data) for k, p in self.params.items()}
-        self.v = {k: torch.zeros_like(p.data) for k, p in self.params.items()}
-        self.g = {k: torch.zeros_like(p.data) for k, p in self.params.items()}
+        self.opt = AdamL2State(dict(model.named_parameters()), betas, eps, weight_decay, "DGPTrainer")
+        self.params, self.m, self.v, self.g = self.opt.params, self.opt.m, self.opt.v, self.opt.g
         self._names = {id(p): k for k, p in self.params.items()}
-        self._bufs = {}
+        self._buf = BufferPool(model.a_att).pool
         self._rows = None
 
-    def _buf(self, key, shape) -> torch.Tensor:
-        b = self._bufs.get(key)
-        if b is None or tuple(b.shape) != tuple(shape):
-            b = self._bufs[key] = torch.empty(shape, dtype=torch.float32, device=self.model.a_att.device)
-        return b
+    @property
+    def t(self) -> int:
+        """Optimiser steps taken; the dropout of step t + 1 uses t + 1."""
+        return self.opt.t
 
     def _side(self, k: int):
         m = self.model
@@ -279,8 +263,7 @@ class DGPTrainer:
     def _prepare(self, x, rows, targets):
         m = self.model
         dev = m.a_att.device
-        if not (torch.is_tensor(x) and x.is_cuda):
-            raise RuntimeError("DGPTrainer needs device tensors: the product path has no CPU fallback")
+        need_device(x, "DGPTrainer")
         x = x.float().contiguous()
         # distinct rows: checked on the host once per rows object (a device tensor costs one copy back, the first time only)
         if self._rows is None or self._rows[0] is not rows:
@@ -354,10 +337,8 @@ class DGPTrainer:
         """One epoch of the reference: forward (dropout where `hidden_layers` has a 'd'), loss, backward, Adam.  Returns the
         training-mode loss as a 0-dim device tensor."""
         x, rows, targets = self._prepare(x, rows, targets)
-        self.t += 1
-        loss = self._forward_backward(x, rows, targets, self.t).clone().reshape(())
-        for k, p in self.params.items():
-            ops.adam_l2(p.data, self.g[k], self.m[k], self.v[k], self.lr, self.t, self.betas, self.eps, self.wd)
+        loss = self._forward_backward(x, rows, targets, self.t + 1).clone().reshape(())
+        self.opt.step(self.lr)
         return loss
 
     @torch.no_grad()

@@ -248,6 +248,7 @@ class DGPEvaluator:
     def __init__(self, graph_edges, nodes: Sequence[str], n_seen: int, pred, consider_trains: bool = False, dtype="f16",
                  device="cuda:0", cnn: Optional[Callable] = None, tree: Optional[ListTree] = None):
         from .. import ops
+        from ._shared import ancestor_tables                           # imports this module
         self.ops = ops
         self.tree = tree if tree is not None else build_list_tree(graph_edges, nodes)
         n = len(self.tree.nodes)
@@ -271,14 +272,7 @@ class DGPEvaluator:
         self.bias = v16[:, self.k].to(torch.float32).to(self.device)
         self.ld = -(-n // 8) * 8                                       # table rows start 16-byte aligned
         self.depth = torch.from_numpy(self.tree.depth.copy()).to(self.device)
-        ptr, anc, lev = [0], [], []
-        for i in range(n):
-            p = self.tree.path(i)
-            anc.extend(p)
-            lev.extend(int(self.tree.depth[q]) for q in p)
-            ptr.append(len(anc))
-        i32 = lambda a: torch.tensor(a, dtype=torch.int32).to(self.device)
-        self._ptr_host, self.anc_ptr, self.anc_nodes, self.anc_levels = ptr, i32(ptr), i32(anc), i32(lev)
+        self._ptr_host, self.anc_ptr, self.anc_nodes, self.anc_levels = ancestor_tables(self.tree, self.device)
         self.acc = torch.zeros((n + 1, 9), dtype=torch.float64, device=self.device)     # one row per class, the last for add_rows
         self._buf, self._cap = None, 0
 

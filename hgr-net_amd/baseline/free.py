@@ -25,19 +25,18 @@ from __future__ import annotations
 import math
 import os
 import types
-from typing import Callable, Dict, Optional, Sequence, Tuple
+from typing import Callable, Dict, Optional, Tuple
 
 import numpy as np
 import torch
 from torch import nn
 
 from .. import ops
-from . import cnzsl
-from .dgp_eval import MAXL, ListTree
+from ._shared import K_SLICE, TOP, BufferPool, TreeScorer, fmix32, mean_rows, need_device, sliced_matmul_f32  # noqa: F401
+from .cnzsl import synth_rows  # noqa: F401
+from .dgp_eval import ListTree
 
 RES = 2048                                   # classifier.py:63,108: `.view(-1, 2048)`
-TOP = cnzsl.TOP
-K_SLICE = cnzsl.K_SLICE
 STREAM_Z, STREAM_EPS = 0, 1                  # counter streams: generator noise, FR reparameterisation noise
 TORCH_DT = {"bf16": torch.bfloat16, "f16": torch.float16, "fp32": torch.float32}
 NO_TRAIN = "{}: this build runs FREE's validation route only (eval mode); training the GAN is the reference's train_free.py"
@@ -68,11 +67,6 @@ def _tdt(dtype) -> torch.dtype:
     return TORCH_DT[dtype]
 
 
-def _need_device(t, what: str) -> None:
-    if not (torch.is_tensor(t) and t.is_cuda):
-        raise RuntimeError(f"FREE needs device tensors ({what}): the product path has no CPU fallback")
-
-
 def _w16(layer: nn.Linear, tdt: torch.dtype, pad_to: int = 0) -> torch.Tensor:
     """The layer's weight in the MFMA type (rows padded with zeros up to `pad_to`), converted again when the weight has changed."""
     w = layer.weight.data
@@ -88,17 +82,14 @@ def _w16(layer: nn.Linear, tdt: torch.dtype, pad_to: int = 0) -> torch.Tensor:
 
 def product(x: torch.Tensor, layer: nn.Linear, dtype: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 x W^T (no bias) of one Linear: 16-bit MFMA with fp32 accumulation, or the fp32 product in slices of K_SLICE columns
-    (one fp32 accumulator chain over thousands of terms drifts from a blocked sum, cnzsl.cosine_logits)."""
+    (one fp32 accumulator chain over thousands of terms drifts from a blocked sum, _shared.sliced_matmul_f32)."""
     n, k = layer.weight.shape
     if x.shape[1] != k:
         raise ValueError(f"input has {x.shape[1]} columns, the layer takes {k}")
     if out is None:
         out = torch.empty((x.shape[0], n), dtype=torch.float32, device=x.device)
     if dtype == "fp32":
-        w = layer.weight.data
-        for j in range(0, k, K_SLICE):
-            e = min(k, j + K_SLICE)
-            ops.matmul_f32(x[:, j:e], w[:, j:e].t(), out, accumulate=j > 0)
+        sliced_matmul_f32(x, layer.weight.data, out)
     else:
         if k % 64:
             raise ValueError(f"K={k} must be a multiple of 64 on the 16-bit route")
@@ -175,8 +166,8 @@ class Generator(_Eval):
     @torch.no_grad()
     def forward(self, z, c=None, dtype: Optional[str] = None):
         self._check_eval()
-        _need_device(z, "z")
-        _need_device(c, "c")
+        need_device(z, "FREE", "z")
+        need_device(c, "FREE", "c")
         dtype = dtype or self.dtype
         rows, nz = z.shape
         inp = torch.empty((rows, nz + c.shape[1]), dtype=_tdt(dtype), device=z.device)
@@ -226,7 +217,7 @@ class FR(_Eval):
     @torch.no_grad()
     def forward(self, feat, train_G: bool = False, eps: Optional[torch.Tensor] = None, seed: int = 0, dtype: Optional[str] = None):
         self._check_eval()
-        _need_device(feat, "feat")
+        need_device(feat, "FREE", "feat")
         dtype = dtype or self.dtype
         res, ngh, a = self.fc1.in_features, self.fc1.out_features, self.attSize
         rows, dev = feat.shape[0], feat.device
@@ -275,10 +266,7 @@ class LinearLogSoftmaxClassifier(_Eval):
         if dtype == "fp32":
             out.zero_()
             out[:, :n].copy_(self.fc.bias.data.expand(x.shape[0], n))
-            w = self.fc.weight.data
-            for j in range(0, k, K_SLICE):
-                e = min(k, j + K_SLICE)
-                ops.matmul_f32(x[:, j:e], w[:, j:e].t(), out, accumulate=True)
+            sliced_matmul_f32(x, self.fc.weight.data, out, accumulate_first=True)
         else:
             if k % 64:
                 raise ValueError(f"K={k} must be a multiple of 64 on the 16-bit route")
@@ -294,7 +282,7 @@ class LinearLogSoftmaxClassifier(_Eval):
     @torch.no_grad()
     def forward(self, x, dtype: Optional[str] = None):
         self._check_eval()
-        _need_device(x, "x")
+        need_device(x, "FREE", "x")
         dtype = dtype or self.dtype
         n = self.fc.out_features
         lg = self.logits(x.to(_tdt(dtype)).contiguous(), dtype)
@@ -309,7 +297,7 @@ def synthesize(generator: Generator, classes, attribute: torch.Tensor, num: int 
     """generate_syn_feature: (features [len(classes) * num, resSize] on the device in the route's type, labels int64): `num` rows
     per class from z ~ N(0, 1) and the class's attribute row, labelled with the class's node index.  The noise of row i is the
     counter normal of (seed, STREAM_Z, i, column): the table does not depend on `chunk_classes`."""
-    _need_device(attribute, "attribute")
+    need_device(attribute, "FREE", "attribute")
     dtype = dtype or generator.dtype
     cls = np.asarray(classes.detach().cpu() if torch.is_tensor(classes) else classes, dtype=np.int64).reshape(-1)
     if cls.size < 1 or cls.min() < 0 or cls.max() >= attribute.shape[0] or num < 1 or chunk_classes < 1:
@@ -365,31 +353,27 @@ def _switch(name: str) -> bool:
     return os.environ.get(name, "1") != "0"
 
 
-class FREEClassifier:
+class FREEClassifier(TreeScorer):
     """classifier.py:45-341 `CLASSIFIER` on cached features.  `tree`: a dgp_eval.ListTree, or (c2p, d2n, ordered_nodes) as gen_tree
-    returns them.  `attribute` [N, A] on the device; `test_index` the candidate node indices (the synthetic classes)."""
+    returns them.  `attribute` [N, A] on the device; `test_index` the candidate node indices (the synthetic classes).  test() counts
+    through _shared.TreeScorer (`add`, `add_rows`, `counters`, `result`; an `eps` behind the targets goes to `log_probs`)."""
 
     def __init__(self, netG: Generator, netFR: FR, tree, test_index, attribute: torch.Tensor, nclass: int, lr: float = 0.001,
                  beta1: float = 0.5, nepoch: int = 20, batch_size: int = 1512, syn_num: int = 100, syn_batch_size: int = 1000,
                  dtype: str = "bf16", seed: int = 0, syn: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                  perm: Optional[Callable[[int], torch.Tensor]] = None):
-        _need_device(attribute, "attribute")
+        need_device(attribute, "FREE", "attribute")
         self.dev, self.dtype, self.tdt = attribute.device, dtype, _tdt(dtype)
         self.netG, self.netFR = netG.to(self.dev).eval(), netFR.to(self.dev).eval()
         if not isinstance(tree, ListTree):
             c2p, d2n, nodes = tree
             depth = np.array([len(c) for c in c2p], dtype=np.int32)
             tree = ListTree(list(nodes), [list(c) for c in c2p], depth, {int(k): list(v) for k, v in dict(d2n).items()}, int(depth.max()) + 1)
-        self.tree = tree
-        n = len(tree.nodes)
-        if tree.n_levels > MAXL:
-            raise ValueError(f"{tree.n_levels} levels: at most {MAXL}")
-        te = np.asarray(test_index.detach().cpu() if torch.is_tensor(test_index) else test_index, dtype=np.int64).reshape(-1)
-        if te.size < max(TOP) or te.min() < 0 or te.max() >= n or np.unique(te).size != te.size:
-            raise ValueError(f"test_index: at least {max(TOP)} distinct node indices below {n}")
+        super().__init__(tree, test_index, self.dev)
+        n, te = self.n, self.test_index
         if attribute.shape[0] != n or nclass < n:
             raise ValueError(f"{attribute.shape[0]} attribute rows and {nclass} classes for {n} nodes")
-        self.test_index, self.attribute, self.nclass, self.n = te, attribute, int(nclass), n
+        self.attribute, self.nclass = attribute, int(nclass)
         self.lr, self.betas, self.nepoch, self.batch_size, self.syn_batch_size, self.seed = lr, (beta1, 0.999), nepoch, int(batch_size), int(syn_batch_size), seed
         res, ngh, a = netFR.fc1.in_features, netFR.fc1.out_features, netFR.attSize
         self.res, self.input_dim = res, res + ngh + a
@@ -411,19 +395,8 @@ class FREEClassifier:
         self.syn_feature, self.syn_label = syn if syn is not None else synthesize(self.netG, te, attribute, syn_num, seed, dtype)
         self.ntrain = self.syn_feature.shape[0]
         self.batcher = SynBatcher(self.ntrain, seed, perm)
-        self._bufs: Dict[str, torch.Tensor] = {}
-        # test(): the evaluator's tables (cnzsl.CNZSLEvaluator)
-        te32 = torch.tensor(te.astype(np.int32), device=self.dev)
-        self.index = ops.EvalIndex(torch.from_numpy(tree.depth.astype(np.int32)).to(self.dev), te32, te32, tree.n_levels)
-        ptr, anc, lev = [0], [], []
-        for i in range(n):
-            path = tree.path(i)
-            anc.extend(path)
-            lev.extend(int(tree.depth[q]) for q in path)
-            ptr.append(len(anc))
-        i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(self.dev)
-        self._ptr_host, self.anc_ptr, self.anc_nodes, self.anc_levels = ptr, i32(ptr), i32(anc), i32(lev)
-        self.acc = torch.zeros(9, dtype=torch.float64, device=self.dev)
+        self._pool = BufferPool(self.dev)
+        self._buf, self._bufs = self._pool.pool, self._pool.bufs
 
     # -- the model's state -------------------------------------------------------------------------------------------------------------------
     def load_model(self, sd: dict) -> None:
@@ -439,17 +412,11 @@ class FREEClassifier:
             self.w16 = torch.empty((self.npad, self.input_dim), dtype=self.tdt, device=self.dev)
             ops.cast16(self.wp, self.w16)
 
-    def _buf(self, key: str, shape, dtype=torch.float32) -> torch.Tensor:
-        b = self._bufs.get(key)
-        if b is None or tuple(b.shape) != tuple(shape) or b.dtype != dtype:
-            b = self._bufs[key] = torch.zeros(shape, dtype=dtype, device=self.dev)
-        return b
-
     # -- inputs ------------------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def features(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """compute_fear_out: cat([x, hidden, h]) [rows, input_dim] in the route's type."""
-        _need_device(x, "x")
+        need_device(x, "FREE", "x")
         if x.dim() != 2 or x.shape[1] != self.res:
             raise ValueError(f"features must be [rows, {self.res}], got {tuple(x.shape)}")
         big = out if out is not None else torch.empty((x.shape[0], self.input_dim), dtype=self.tdt, device=self.dev)
@@ -480,15 +447,12 @@ class FREEClassifier:
         lab = labels.reshape(-1).to(torch.int32)
         logits = self.model_logits(big, self._buf("logits", (b, npad)))
         loss_rows, loss = self._buf("loss_rows", (b,)), self._buf("loss", (1,))
-        ones = self._bufs.get("ones")
-        if ones is None or ones.numel() != b:
-            ones = self._bufs["ones"] = torch.ones(b, dtype=torch.float32, device=self.dev)
         self.t += 1
         d16 = self._buf("d16", (b, npad), self.tdt)
         if self.nll_fused:
             ops.nll_rows16(logits, lab, n=n, loss_rows=loss_rows, dlogits=d16)
         else:
-            d32 = self._buf("d32", (b, npad))              # its padding columns stay zero
+            d32 = self._buf("d32", (b, npad), zero=True)   # ce_rows writes n columns: the padding columns stay zero
             ops.ce_rows(logits[:, :n], lab, loss_rows, d32, gscale=1.0)
             ops.cast16(d32, d16)
         s0 = ops.tn_slices(npad, k, b)
@@ -506,7 +470,7 @@ class FREEClassifier:
             ops.cast16(self.wp, self.w16)
         ops.colsum(d16, gb, self._buf("cs", ((b + 511) // 512 * npad,)), accumulate=False, alpha=1.0 / b)
         ops.adam_l2(self.bp, gb, self.mb, self.vb, self.lr, self.t, self.betas)
-        return ops.dot_f32(loss_rows, ones, loss, alpha=1.0 / b).clone().reshape(())
+        return mean_rows(self._pool, loss_rows, loss).clone().reshape(())
 
     def model_logits(self, big: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         """fc(big) [rows, Npad] fp32 from the master weights (their 16-bit copy on the 16-bit routes)."""
@@ -517,8 +481,8 @@ class FREEClassifier:
     @torch.no_grad()
     def step(self, real_feats: torch.Tensor, real_labels: torch.Tensor, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One iteration of fit_zsl's loop body: the batch is exactly `batch_size` rows (classifier.py:111 copies into a fixed buffer)."""
-        _need_device(real_feats, "real_feats")
-        _need_device(real_labels, "real_labels")
+        need_device(real_feats, "FREE", "real_feats")
+        need_device(real_labels, "FREE", "real_labels")
         if real_feats.shape[0] + self.syn_batch_size != self.batch_size:
             raise ValueError(f"{real_feats.shape[0]} real + {self.syn_batch_size} synthetic rows do not fill the [{self.batch_size}, {self.input_dim}] buffer")
         big, lab = self.next_batch(real_feats, real_labels, eps=eps, out=self._buf("big", (self.batch_size, self.input_dim), self.tdt))
@@ -545,25 +509,7 @@ class FREEClassifier:
         ops.nll_rows16(lg, None, n=self.nclass, logsm=lg)
         return lg
 
-    @torch.no_grad()
-    def add(self, feats: torch.Tensor, target: int, eps: Optional[torch.Tensor] = None):
-        """One batch of ONE class (the reference's test loader); returns the device outputs (pred [B, 20], top1 [B, 1], lv)."""
-        t = int(target)
-        if not 0 <= t < self.n:
-            raise ValueError(f"target {target} outside the {self.n} nodes")
-        lv, top1, pred = ops.eval_rows(self.log_probs(feats, eps), self.index, max(TOP))
-        o, e = self._ptr_host[t], self._ptr_host[t + 1]
-        ops.eval_counters(pred, None, t, top1.view(-1), lv, self.anc_nodes[o:e], self.anc_levels[o:e], self.acc)
-        return pred, top1, lv
-
-    @torch.no_grad()
-    def add_rows(self, feats: torch.Tensor, targets: torch.Tensor, eps: Optional[torch.Tensor] = None):
-        """One batch of MIXED classes: `targets` [B] on the device, node indices."""
-        if not (torch.is_tensor(targets) and targets.is_cuda and targets.numel() == feats.shape[0]):
-            raise ops._lib.HgrError("targets must be a device tensor with one node index per row")
-        lv, top1, pred = ops.eval_rows(self.log_probs(feats, eps), self.index, max(TOP))
-        ops.eval_counters_rows(pred, targets.to(torch.int64).contiguous().view(-1), top1.view(-1), lv, self.anc_ptr, self.anc_nodes, self.anc_levels, self.acc)
-        return pred, top1, lv
+    scores = log_probs
 
     def test(self, loader) -> str:
         """`loader`: (features [b, resSize], the batch's one target) pairs; returns the metric string."""
@@ -571,34 +517,18 @@ class FREEClassifier:
             self.add(feats, target)
         return self.result()
 
-    def counters(self) -> np.ndarray:
-        return self.acc.cpu().numpy()
-
-    def result(self) -> str:
-        return cnzsl.metric_string(self.counters())
-
 
 # ---- host twins: plain torch / numpy ------------------------------------------------------------------------------------------------------
-def _fmix32(h: np.ndarray) -> np.ndarray:
-    h = h.astype(np.uint64) & 0xFFFFFFFF
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-    h ^= h >> 16
-    return h
-
-
 def normal_bits_host(seed: int, stream: int, row0: int, rows: int, cols: int) -> Tuple[np.ndarray, np.ndarray]:
     """The two 32-bit draws (a, b), uint32 [rows, cols], of hgr_normal_counter (include/hgr.h)."""
     m = 0xFFFFFFFF
-    key = _fmix32(np.array(((seed & m) + 0x9E3779B9 * ((stream & m) + 1)) & m, dtype=np.uint64))
-    key = _fmix32(key ^ 0xC2B2AE35)
+    key = fmix32(np.array(((seed & m) + 0x9E3779B9 * ((stream & m) + 1)) & m, dtype=np.uint64))
+    key = fmix32(key ^ 0xC2B2AE35)
     r = np.arange(row0, row0 + rows, dtype=np.uint64)
-    rk = _fmix32(key ^ (r & m))
-    rk = _fmix32((rk + 0x9E3779B9 * ((r >> 32) + 1)) & m)[:, None]
+    rk = fmix32(key ^ (r & m))
+    rk = fmix32((rk + 0x9E3779B9 * ((r >> 32) + 1)) & m)[:, None]
     c = np.arange(cols, dtype=np.uint64)[None, :]
-    return _fmix32(rk ^ ((2 * c) & m)).astype(np.uint32), _fmix32(rk ^ ((2 * c + 1) & m)).astype(np.uint32)
+    return fmix32(rk ^ ((2 * c) & m)).astype(np.uint32), fmix32(rk ^ ((2 * c + 1) & m)).astype(np.uint32)
 
 
 def normal_host(seed: int, stream: int, row0: int, rows: int, cols: int) -> np.ndarray:
@@ -667,10 +597,6 @@ def fit_step_host(state: dict, big, labels, lr: float = 0.001, betas=(0.5, 0.999
 
 
 # ---- synthetic material (hgr_net_amd.synth: a pure function of the seed) -----------------------------------------------------------------
-def synth_rows(seed: int, name: str, rows: int, cols: int) -> np.ndarray:
-    return cnzsl.synth_rows(seed, name, rows, cols)
-
-
 def synth_state(seed: int, opt, which: str, att_gain: float = 1.0) -> Dict[str, np.ndarray]:
     """A state dict of fp32 arrays for `which` = 'netG' or 'netFR': fan-in scaled normal weights (the outputs spread over (0, 1)
     instead of sitting at sigmoid(0)), small normal biases.  `att_gain` multiplies the generator's weights on the attribute half of

@@ -14,7 +14,7 @@
 // memory once; beyond that every pass re-reads the strip from L2 (a thread only ever re-reads what it wrote itself).
 // Summation order: per thread its rows in ascending order, then a shuffle tree over the 16 row slots of a wave, then the
 // workgroup's waves in order - a function of S alone, never of the grid.  No atomics, nothing allocated.
-#include "hgr_common.h"
+#include "hgr_rows.h"
 
 namespace {
 
@@ -237,8 +237,6 @@ int cn_lds(K kernel, bool &granted, int S, size_t &bytes, const char *name) {
     return HGR_OK;
 }
 
-bool cn_ok4(const void *p, int64_t ld, int H) { return hgr_aligned(p, 16) && ld % 4 == 0 && ld >= H; }
-
 }  // namespace
 
 extern "C" int hgr_cnzsl_std_chain_fwd(const float *z, int64_t ld_z, const float *bias, float *running_mean1, float *running_var1,
@@ -248,7 +246,7 @@ extern "C" int hgr_cnzsl_std_chain_fwd(const float *z, int64_t ld_z, const float
     HGR_REQUIRE(H >= 4 && H % 4 == 0, "hgr_cnzsl_std_chain_fwd: H=%d must be a multiple of 4", H);
     HGR_REQUIRE(train ? S >= 2 : S >= 1, "hgr_cnzsl_std_chain_fwd: S=%d (training needs two classes for the unbiased variance, evaluation one)", S);
     HGR_REQUIRE(!train || (a && stats), "hgr_cnzsl_std_chain_fwd: training writes a and stats");
-    HGR_REQUIRE(cn_ok4(z, ld_z, H) && cn_ok4(c, ld_c, H) && (!a || cn_ok4(a, ld_a, H)),
+    HGR_REQUIRE(rows_f32_ok(z, ld_z, H) && rows_f32_ok(c, ld_c, H) && (!a || rows_f32_ok(a, ld_a, H)),
                 "hgr_cnzsl_std_chain_fwd: z / c / a must be 16-byte aligned, leading dimensions multiples of 4 and >= H");
     HGR_REQUIRE(hgr_aligned(bias, 16) && hgr_aligned(running_mean1, 16) && hgr_aligned(running_var1, 16) && hgr_aligned(running_mean2, 16) &&
                 hgr_aligned(running_var2, 16) && hgr_aligned(stats, 16), "hgr_cnzsl_std_chain_fwd: vectors must be 16-byte aligned");
@@ -276,7 +274,7 @@ extern "C" int hgr_cnzsl_std_chain_bwd(const float *dc, int64_t ld_dc, const flo
                                        float eps, void *stream) {
     HGR_REQUIRE(dc && a && z && bias && stats && dz && dbias, "hgr_cnzsl_std_chain_bwd: null operand");
     HGR_REQUIRE(H >= 4 && H % 4 == 0 && S >= 2, "hgr_cnzsl_std_chain_bwd: S=%d H=%d (S >= 2, H a multiple of 4)", S, H);
-    HGR_REQUIRE(cn_ok4(dc, ld_dc, H) && cn_ok4(a, ld_a, H) && cn_ok4(z, ld_z, H) && cn_ok4(dz, ld_dz, H),
+    HGR_REQUIRE(rows_f32_ok(dc, ld_dc, H) && rows_f32_ok(a, ld_a, H) && rows_f32_ok(z, ld_z, H) && rows_f32_ok(dz, ld_dz, H),
                 "hgr_cnzsl_std_chain_bwd: dc / a / z / dz must be 16-byte aligned, leading dimensions multiples of 4 and >= H");
     HGR_REQUIRE(hgr_aligned(bias, 16) && hgr_aligned(stats, 16) && hgr_aligned(dbias, 16), "hgr_cnzsl_std_chain_bwd: vectors must be 16-byte aligned");
     HGR_REQUIRE(dz != dc && dz != a && dz != z, "hgr_cnzsl_std_chain_bwd: dz must not alias an input");
@@ -296,7 +294,7 @@ extern "C" int hgr_cnzsl_std_chain_bwd(const float *dc, int64_t ld_dc, const flo
 
 extern "C" int hgr_bias_relu_f32(const float *x, int64_t ld_x, const float *bias, float *y, int64_t ld_y, int rows, int C, void *stream) {
     HGR_REQUIRE(x && bias && y && rows >= 1 && C >= 4 && C % 4 == 0, "hgr_bias_relu_f32: bad arguments (C=%d must be a multiple of 4)", C);
-    HGR_REQUIRE(cn_ok4(x, ld_x, C) && cn_ok4(y, ld_y, C) && hgr_aligned(bias, 16),
+    HGR_REQUIRE(rows_f32_ok(x, ld_x, C) && rows_f32_ok(y, ld_y, C) && hgr_aligned(bias, 16),
                 "hgr_bias_relu_f32: x / y / bias must be 16-byte aligned, leading dimensions multiples of 4 and >= C");
     int64_t blocks = ((int64_t)rows * (C / 4) + NT - 1) / NT;
     if (blocks > 4096) blocks = 4096;
@@ -308,7 +306,7 @@ extern "C" int hgr_bias_relu_f32(const float *x, int64_t ld_x, const float *bias
 extern "C" int hgr_relu_bwd_colsum_f32(const float *dy, int64_t ld_dy, const float *y, int64_t ld_y, float *dx, int64_t ld_dx, float *db,
                                        float *scratch, int rows, int C, void *stream) {
     HGR_REQUIRE(dy && y && dx && db && rows >= 1 && C >= 4 && C % 4 == 0, "hgr_relu_bwd_colsum_f32: bad arguments (C=%d must be a multiple of 4)", C);
-    HGR_REQUIRE(cn_ok4(dy, ld_dy, C) && cn_ok4(y, ld_y, C) && cn_ok4(dx, ld_dx, C) && hgr_aligned(db, 16) && hgr_aligned(scratch, 16),
+    HGR_REQUIRE(rows_f32_ok(dy, ld_dy, C) && rows_f32_ok(y, ld_y, C) && rows_f32_ok(dx, ld_dx, C) && hgr_aligned(db, 16) && hgr_aligned(scratch, 16),
                 "hgr_relu_bwd_colsum_f32: operands must be 16-byte aligned, leading dimensions multiples of 4 and >= C");
     const int chunks = (rows + RB_ROWS - 1) / RB_ROWS;
     HGR_REQUIRE(chunks <= 65535, "hgr_relu_bwd_colsum_f32: rows=%d beyond %d", rows, 65535 * RB_ROWS);

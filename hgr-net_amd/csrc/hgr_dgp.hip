@@ -12,20 +12,11 @@
 // Descendant-side operators are extremely skewed (the root aggregates every node), so long rows are cut into several
 // items: a row with one item is finished in place (LeakyReLU, row L2 norm via wave shuffles + LDS), a row with several
 // writes fp32 partials that `csr_finish` adds in item order - deterministic, no atomics.
-#include "hgr_common.h"
+#include "hgr_rows.h"
 
 namespace {
 
 constexpr int NT = 256;
-
-__device__ __forceinline__ float block_sum(float v, float *red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // finish a row held as float4 slices in registers: activation, optional L2 normalisation, store
 template <int NV>
@@ -158,10 +149,7 @@ extern "C" int hgr_csr_group_aggregate(const float *support, int64_t ld_support,
             hipLaunchKernelGGL(csr_finish<NV>, dim3(n_split), dim3(NT), 0, s, split_row, split_slot0, split_n, partial, out, ld_out, \
                                C, slope, normalize);                                                                                \
     } while (0)
-    if (nv == 1) HGR_DGP_LAUNCH(1);
-    else if (nv == 2) HGR_DGP_LAUNCH(2);
-    else if (nv == 3) HGR_DGP_LAUNCH(3);
-    else HGR_DGP_LAUNCH(4);
+    HGR_NV_LADDER(nv, HGR_DGP_LAUNCH);
 #undef HGR_DGP_LAUNCH
     HGR_CHECK_LAUNCH("hgr_csr_group_aggregate");
     return HGR_OK;

@@ -12,20 +12,11 @@
 // Same structure as the forward gather: a workgroup owns one work item (at most CHUNK edges of one row), its 256 threads
 // own float4 column slices, edge data is block-uniform, rows cut into several items leave fp32 partials that a finish
 // kernel adds in item order.  No atomics: a launch repeated on the same inputs gives bit-equal output.
-#include "hgr_common.h"
+#include "hgr_rows.h"
 
 namespace {
 
 constexpr int NT = 256;
-
-__device__ __forceinline__ float block_sum(float v, float *red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // dO slices of one row: G * (Y > 0 ? 1 : slope), or G itself without Y (the last layer, whose dO the loss head made)
 template <int NV>
@@ -204,12 +195,6 @@ __global__ __launch_bounds__(NT) void loss_sum(const float *__restrict__ loss_ro
     if (threadIdx.x == 0) *loss = s;
 }
 
-// murmur3's 32-bit finaliser
-__host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-
 __global__ __launch_bounds__(NT) void dropout_counter(const float *x, int64_t ldx, float *y, int64_t ldy, int rows, int C, unsigned key) {
     const int64_t q = (int64_t)blockIdx.x * NT + threadIdx.x, per_row = C / 4;
     if (q >= (int64_t)rows * per_row) return;
@@ -226,13 +211,9 @@ __global__ __launch_bounds__(NT) void dropout_counter(const float *x, int64_t ld
 __global__ __launch_bounds__(NT) void adam_l2(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
                                               int64_t n, float beta1, float beta2, float eps, float wd, float step_size, float inv_sqrt_bc2) {
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
-        const float pi = p[i];
-        const float gi = g[i] + wd * pi;                   // coupled decay: part of the gradient the moments see
-        const float mi = m[i] + (gi - m[i]) * (1.f - beta1);
-        const float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = pi - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+        float pi = p[i];
+        adam_l2_update(pi, g[i], m[i], v[i], beta1, beta2, eps, wd, step_size, inv_sqrt_bc2);
+        p[i] = pi;
     }
 }
 
@@ -263,10 +244,7 @@ extern "C" int hgr_csr_group_att_grad(const float *support, int64_t ld_support, 
             hipLaunchKernelGGL(csr_att_grad_finish<NV>, dim3(n_split), dim3(NT), 0, s, split_row, split_slot0, split_n, partial, P, \
                                D, g, ld_g, y, ld_y, dout, ld_dout, C, slope);                                                       \
     } while (0)
-    if (nv == 1) HGR_DGP_LAUNCH(1);
-    else if (nv == 2) HGR_DGP_LAUNCH(2);
-    else if (nv == 3) HGR_DGP_LAUNCH(3);
-    else HGR_DGP_LAUNCH(4);
+    HGR_NV_LADDER(nv, HGR_DGP_LAUNCH);
 #undef HGR_DGP_LAUNCH
     HGR_CHECK_LAUNCH("hgr_csr_group_att_grad");
     return HGR_OK;
@@ -284,10 +262,9 @@ extern "C" int hgr_dgp_loss_head(const float *O, int64_t ld_o, const int *rows, 
     if (hipMemset2DAsync(dout, (size_t)ld_dout * sizeof(float), 0, (size_t)C * sizeof(float), (size_t)n, s) != hipSuccess)
         return hgr_set_error(HGR_ELAUNCH, "hgr_dgp_loss_head: clearing dout failed");
     const int nv = (C + 4 * NT - 1) / (4 * NT);
-    if (nv == 1) hipLaunchKernelGGL(loss_head<1>, dim3(n_t), dim3(NT), 0, s, O, ld_o, rows, F, ld_f, n_t, loss_rows, dout, ld_dout, C);
-    else if (nv == 2) hipLaunchKernelGGL(loss_head<2>, dim3(n_t), dim3(NT), 0, s, O, ld_o, rows, F, ld_f, n_t, loss_rows, dout, ld_dout, C);
-    else if (nv == 3) hipLaunchKernelGGL(loss_head<3>, dim3(n_t), dim3(NT), 0, s, O, ld_o, rows, F, ld_f, n_t, loss_rows, dout, ld_dout, C);
-    else hipLaunchKernelGGL(loss_head<4>, dim3(n_t), dim3(NT), 0, s, O, ld_o, rows, F, ld_f, n_t, loss_rows, dout, ld_dout, C);
+#define HGR_DGP_LAUNCH(NV) hipLaunchKernelGGL(loss_head<NV>, dim3(n_t), dim3(NT), 0, s, O, ld_o, rows, F, ld_f, n_t, loss_rows, dout, ld_dout, C)
+    HGR_NV_LADDER(nv, HGR_DGP_LAUNCH);
+#undef HGR_DGP_LAUNCH
     hipLaunchKernelGGL(loss_sum, dim3(1), dim3(NT), 0, s, loss_rows, n_t, loss);
     HGR_CHECK_LAUNCH("hgr_dgp_loss_head");
     return HGR_OK;

@@ -12,7 +12,7 @@
 // All of them are bound by memory: a lane moves 16 bytes per access, a 16-bit value is ONE rounding of the fp32 value, sums run in
 // a fixed order (per thread ascending, a shuffle tree over the wave, the waves in order) and nothing is atomic - a launch
 // repeated on the same input writes the same bits.
-#include "hgr_common.h"
+#include "hgr_rows.h"
 #include <math.h>
 
 namespace {
@@ -20,12 +20,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int OUT_F32 = 2;                      // `out_type`: HGR_BF16, HGR_F16 or fp32
 constexpr int NLL_RES = HGR_NLL_RESIDENT_COLS;  // a row of up to this many fp32 logits stays in LDS (72 KiB: two workgroups per CU)
-
-// murmur3's 32-bit finaliser (hgr_dropout_counter's mix)
-__host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
 
 // ---- the counter normal: free.normal_host is the float64 twin of these three functions ---------------------------------------------
 unsigned normal_key(int seed, int stream) {
@@ -186,20 +180,6 @@ __global__ __launch_bounds__(NT) void fr_tail(const float *__restrict__ lat, int
 }
 
 // ---- hgr_nll_rows16: one workgroup per row -------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_max(float v, float *red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ float block_sum(float v, float *red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 // two running (max, sum of exp(x - max)) states into one; symmetric, so both lanes of an exchange hold the same bits
 __device__ __forceinline__ void online_merge(float &m, float &s, float m2, float s2) {
     const float mn = fmaxf(m, m2);
@@ -287,7 +267,7 @@ __global__ __launch_bounds__(NT) void nll_rows16(const float *logits, int64_t ld
     }
 }
 
-// g' = alpha (g[0] + g[1] + ...), then hgr_adam_l2's statements on it (the product is handed over through an opaque register copy, so
+// g' = alpha (g[0] + g[1] + ...), then hgr_adam_l2's update (adam_l2_update) on it (the product is handed over through an opaque register copy, so
 // that it is rounded before the decay term meets it, as a gradient read from memory is), then the 16-bit copy of the new parameter
 template <int DT>
 __global__ __launch_bounds__(NT) void adam_l2_cast16(float *__restrict__ p, const float *__restrict__ g, int64_t slice_stride, int S, float alpha,
@@ -301,13 +281,11 @@ __global__ __launch_bounds__(NT) void adam_l2_cast16(float *__restrict__ p, cons
         for (int e = 0; e < 4; ++e) {
             float ga = alpha * gs[e];
             asm volatile("" : "+v"(ga));
-            const float pi = pv[e];
-            const float gi = ga + wd * pi;
-            const float mi = mv[e] + (gi - mv[e]) * (1.f - beta1);
-            const float vi = vv[e] * beta2 + (1.f - beta2) * gi * gi;
-            mv[e] = mi;
-            vv[e] = vi;
-            pv[e] = pi - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+            float pe = pv[e], me = mv[e], ve = vv[e];         // a vector element does not bind to a float &
+            adam_l2_update(pe, ga, me, ve, beta1, beta2, eps, wd, step_size, inv_sqrt_bc2);
+            pv[e] = pe;
+            mv[e] = me;
+            vv[e] = ve;
         }
         ((f32x4 *)m)[i] = mv;
         ((f32x4 *)v)[i] = vv;
@@ -325,7 +303,6 @@ unsigned grid_for(int64_t items) {
 bool out_ok(const void *y, int64_t ld, int C) {
     return y && ld % 8 == 0 && ld >= C && hgr_aligned(y, 16);
 }
-bool f32_ok(const void *x, int64_t ld, int C) { return x && ld % 4 == 0 && ld >= C && hgr_aligned(x, 16); }
 
 #define HGR_OT_OK(name) HGR_REQUIRE(out_type == HGR_BF16 || out_type == HGR_F16 || out_type == OUT_F32, name ": out_type must be HGR_BF16, HGR_F16 or 2 (fp32)")
 #define HGR_OT_LAUNCH(kernel, ...)                                                                  \
@@ -339,7 +316,7 @@ bool f32_ok(const void *x, int64_t ld, int C) { return x && ld % 4 == 0 && ld >=
 
 extern "C" int hgr_normal_counter(float *z, int64_t ld_z, uint32_t *bits, int rows, int C, int seed, int stream_id, int64_t row0, void *stream) {
     HGR_REQUIRE(z && rows >= 1 && C >= 4 && C % 4 == 0 && row0 >= 0, "hgr_normal_counter: bad arguments (C=%d must be a multiple of 4, row0 >= 0)", C);
-    HGR_REQUIRE(f32_ok(z, ld_z, C) && hgr_aligned(bits, 16), "hgr_normal_counter: z / bits must be 16-byte aligned, ld_z a multiple of 4 and >= C");
+    HGR_REQUIRE(rows_f32_ok(z, ld_z, C) && hgr_aligned(bits, 16), "hgr_normal_counter: z / bits must be 16-byte aligned, ld_z a multiple of 4 and >= C");
     hipLaunchKernelGGL(normal_counter, dim3(grid_for((int64_t)rows * (C / 4))), dim3(NT), 0, (hipStream_t)stream, z, ld_z, (unsigned *)bits, rows, C,
                        normal_key(seed, stream_id), row0);
     HGR_CHECK_LAUNCH("hgr_normal_counter");
@@ -354,7 +331,7 @@ extern "C" int hgr_free_gen_input(void *out, int64_t ld_out, int out_type, const
     HGR_REQUIRE(rows >= 1 && num >= 1 && n_classes >= 1 && att_rows >= 1 && row0 >= 0 && row0 + rows <= (int64_t)n_classes * num,
                 "hgr_free_gen_input: rows [%lld, %lld) outside the %d x %d synthetic rows", (long long)row0, (long long)(row0 + rows), n_classes, num);
     HGR_REQUIRE(nz >= 8 && nz % 8 == 0 && A >= 8 && A % 8 == 0, "hgr_free_gen_input: nz=%d and A=%d must be multiples of 8", nz, A);
-    HGR_REQUIRE(out_ok(out, ld_out, nz + A) && f32_ok(att, ld_att, A) && (!z || f32_ok(z, ld_z, nz)),
+    HGR_REQUIRE(out_ok(out, ld_out, nz + A) && rows_f32_ok(att, ld_att, A) && (!z || rows_f32_ok(z, ld_z, nz)),
                 "hgr_free_gen_input: out / att / z must be 16-byte aligned, ld_out a multiple of 8 and >= nz + A, ld_att / ld_z multiples of 4 and >= A / nz");
     const dim3 grid(grid_for((int64_t)rows * ((nz + A) / 8))), block(NT);
     HGR_OT_LAUNCH(gen_input, grid, block, 0, (hipStream_t)stream, out, ld_out, z, ld_z, att, ld_att, att_rows, classes, n_classes, num, rows, nz, A,
@@ -369,7 +346,7 @@ extern "C" int hgr_bias_act_rows(const float *x, int64_t ld_x, const float *bias
     HGR_OT_OK("hgr_bias_act_rows");
     HGR_REQUIRE(act == HGR_ACT_LRELU02 || act == HGR_ACT_SIGMOID, "hgr_bias_act_rows: act=%d (0 LeakyReLU(0.2), 1 sigmoid)", act);
     HGR_REQUIRE(rows >= 1 && C >= 8 && C % 8 == 0 && col0 >= 0 && col0 % 8 == 0, "hgr_bias_act_rows: C=%d and col0=%lld must be multiples of 8", C, (long long)col0);
-    HGR_REQUIRE(f32_ok(x, ld_x, C) && hgr_aligned(bias, 16) && out_ok(y, ld_y, 0) && ld_y >= col0 + C,
+    HGR_REQUIRE(rows_f32_ok(x, ld_x, C) && hgr_aligned(bias, 16) && out_ok(y, ld_y, 0) && ld_y >= col0 + C,
                 "hgr_bias_act_rows: x / bias / y must be 16-byte aligned, ld_x a multiple of 4 and >= C, ld_y a multiple of 8 and >= col0 + C");
     void *yo = out_type == OUT_F32 ? (void *)((float *)y + col0) : (void *)((unsigned short *)y + col0);
     const dim3 grid(grid_for((int64_t)rows * (C / 8))), block(NT);
@@ -390,7 +367,7 @@ extern "C" int hgr_free_fr_tail(const float *lantent, int64_t ld_l, const float 
     HGR_REQUIRE(lantent && y, "hgr_free_fr_tail: null operand");
     HGR_OT_OK("hgr_free_fr_tail");
     HGR_REQUIRE(rows >= 1 && A >= 8 && A % 8 == 0 && col0 >= 0 && col0 % 8 == 0 && row0 >= 0, "hgr_free_fr_tail: A=%d and col0=%lld must be multiples of 8", A, (long long)col0);
-    HGR_REQUIRE(f32_ok(lantent, ld_l, 2 * A) && hgr_aligned(bias, 16) && (!eps || f32_ok(eps, ld_eps, A)) && (!mus || f32_ok(mus, ld_mus, A)) &&
+    HGR_REQUIRE(rows_f32_ok(lantent, ld_l, 2 * A) && hgr_aligned(bias, 16) && (!eps || rows_f32_ok(eps, ld_eps, A)) && (!mus || rows_f32_ok(mus, ld_mus, A)) &&
                 out_ok(y, ld_y, 0) && ld_y >= col0 + A,
                 "hgr_free_fr_tail: operands must be 16-byte aligned, ld_l / ld_eps / ld_mus multiples of 4 and >= 2A / A / A, ld_y a multiple of 8 and >= col0 + A");
     void *yo = out_type == OUT_F32 ? (void *)((float *)y + col0) : (void *)((unsigned short *)y + col0);
