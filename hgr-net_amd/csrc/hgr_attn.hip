@@ -17,7 +17,7 @@
 //                    transposed image is written.  No LDS round trip for P.
 // Output lane layout: 4 consecutive head dims of one query -> 8-byte stores.
 // HBM-bound in practice (reads 3W, writes W 16-bit values per token), the MFMA work is ~1 % of a layer.
-#include "hgr_common.h"
+#include "hgr_launch.h"
 
 namespace {
 
@@ -183,8 +183,7 @@ template <int DT, int KT>
 void launch_kt(const void *qkv, void *out, int B, int L, int H, bool causal, hipStream_t s, float2 *stats, int ql) {
     typedef typename T16<DT>::elem E;
     dim3 grid(B * H), block(256);
-    if (causal) hipLaunchKernelGGL((mha_fwd<DT, KT, true>), grid, block, 0, s, (const E *)qkv, (E *)out, L, H, stats, ql);
-    else hipLaunchKernelGGL((mha_fwd<DT, KT, false>), grid, block, 0, s, (const E *)qkv, (E *)out, L, H, stats, ql);
+    hgr_by_flag(causal, [&](auto caus) { hipLaunchKernelGGL((mha_fwd<DT, KT, caus.value>), grid, block, 0, s, (const E *)qkv, (E *)out, L, H, stats, ql); });
 }
 
 template <int DT>
@@ -207,8 +206,7 @@ static int mha_entry(const char *name, const void *qkv, void *out, float *stats,
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "%s: bad dtype %d", name, dtype);
     HGR_REQUIRE(q_rows >= 0 && q_rows <= L, "%s: q_rows=%d must lie in [1, L]", name, q_rows);
     const int ql = q_rows ? q_rows : L;
-    if (dtype == HGR_BF16) launch_dt<HGR_BF16>(qkv, out, B, L, heads, causal != 0, (hipStream_t)stream, (float2 *)stats, ql);
-    else launch_dt<HGR_F16>(qkv, out, B, L, heads, causal != 0, (hipStream_t)stream, (float2 *)stats, ql);
+    hgr_by_dtype(dtype, [&](auto dt) { launch_dt<dt.value>(qkv, out, B, L, heads, causal != 0, (hipStream_t)stream, (float2 *)stats, ql); });
     HGR_CHECK_LAUNCH(name);
     return HGR_OK;
 }

@@ -9,7 +9,7 @@
 // channels of one tap) is a single conflict-free ds_read_b128 per lane: pixel p's 64 bytes are 4 chunks, chunk ^= (p >> 2) & 3.
 // Each wave computes 4 output rows x 16 columns x Cout; results leave through LDS as whole 16-byte chunks of contiguous
 // NHWC rows.
-#include "hgr_common.h"
+#include "hgr_launch.h"
 
 namespace {
 
@@ -302,29 +302,18 @@ int hgr_conv3x3_c32_launch(const void *x, const void *w, const float *bias, void
     dim3 grid((unsigned)std::min<int64_t>(nwg, C == 64 ? 256 : 512));           // persistent: 2 (C = 64: 1) workgroups per CU walk over the tiles
     hipStream_t s = (hipStream_t)stream;
     if (C == 64) {                                  // 64 -> 64 channels (ModifiedResNet layer1): 8 waves, one workgroup per CU
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((conv3x3_c32<HGR_BF16, 4, false, 64>), grid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_c32<HGR_F16, 4, false, 64>), grid, dim3(512), 0, s, a);
+        hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((conv3x3_c32<dt.value, 4, false, 64>), grid, dim3(512), 0, s, a); });
         HGR_CHECK_LAUNCH("hgr_conv3x3_nhwc");
         return HGR_OK;
     }
     if (pool) {
-        if (Cout == 32) {
-            if (dtype == HGR_BF16) hipLaunchKernelGGL((conv3x3_c32<HGR_BF16, 2, true>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((conv3x3_c32<HGR_F16, 2, true>), grid, dim3(256), 0, s, a);
-        } else {
-            if (dtype == HGR_BF16) hipLaunchKernelGGL((conv3x3_c32<HGR_BF16, 4, true>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((conv3x3_c32<HGR_F16, 4, true>), grid, dim3(256), 0, s, a);
-        }
+        if (Cout == 32) hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((conv3x3_c32<dt.value, 2, true>), grid, dim3(256), 0, s, a); });
+        else hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((conv3x3_c32<dt.value, 4, true>), grid, dim3(256), 0, s, a); });
         HGR_CHECK_LAUNCH("hgr_conv3x3_pool2_nhwc");
         return HGR_OK;
     }
-    if (Cout == 32) {
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((conv3x3_c32<HGR_BF16, 2>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_c32<HGR_F16, 2>), grid, dim3(256), 0, s, a);
-    } else {
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((conv3x3_c32<HGR_BF16, 4>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_c32<HGR_F16, 4>), grid, dim3(256), 0, s, a);
-    }
+    if (Cout == 32) hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((conv3x3_c32<dt.value, 2>), grid, dim3(256), 0, s, a); });
+    else hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((conv3x3_c32<dt.value, 4>), grid, dim3(256), 0, s, a); });
     HGR_CHECK_LAUNCH("hgr_conv3x3_nhwc");
     return HGR_OK;
 }
@@ -347,13 +336,8 @@ extern "C" int hgr_stem_conv1(const float *image, const void *w, const float *bi
     HGR_REQUIRE(lds <= 64 * 1024, "hgr_stem_conv1: R=%d needs %zu bytes of LDS", R, lds);
     dim3 grid((unsigned)(B * a.tiles_y));
     hipStream_t s = (hipStream_t)stream;
-    if (nout <= 2) {
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((stem_conv1<HGR_BF16, 2>), grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((stem_conv1<HGR_F16, 2>), grid, dim3(256), lds, s, a);
-    } else {
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((stem_conv1<HGR_BF16, 3>), grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((stem_conv1<HGR_F16, 3>), grid, dim3(256), lds, s, a);
-    }
+    if (nout <= 2) hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((stem_conv1<dt.value, 2>), grid, dim3(256), lds, s, a); });
+    else hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((stem_conv1<dt.value, 3>), grid, dim3(256), lds, s, a); });
     HGR_CHECK_LAUNCH("hgr_stem_conv1");
     return HGR_OK;
 }

@@ -141,16 +141,13 @@ extern "C" int hgr_csr_group_aggregate(const float *support, int64_t ld_support,
     HGR_REQUIRE(n_split == 0 || (split_row && split_slot0 && split_n && partial), "hgr_csr_group_aggregate: split rows need their tables and the partial buffer");
     hipStream_t s = (hipStream_t)stream;
     const int nv = (C + 4 * NT - 1) / (4 * NT);
-#define HGR_DGP_LAUNCH(NV)                                                                                                          \
-    do {                                                                                                                            \
-        hipLaunchKernelGGL(csr_aggregate<NV>, dim3(n_items), dim3(NT), 0, s, support, ld_support, item_row, item_e0, item_e1,       \
-                           item_slot, col, inv_deg, grp, att, D, bias, out, ld_out, partial, C, slope, normalize);                  \
-        if (n_split > 0)                                                                                                            \
-            hipLaunchKernelGGL(csr_finish<NV>, dim3(n_split), dim3(NT), 0, s, split_row, split_slot0, split_n, partial, out, ld_out, \
-                               C, slope, normalize);                                                                                \
-    } while (0)
-    HGR_NV_LADDER(nv, HGR_DGP_LAUNCH);
-#undef HGR_DGP_LAUNCH
+    hgr_by_nv4(nv, [&](auto NV) {
+        hipLaunchKernelGGL(csr_aggregate<NV.value>, dim3(n_items), dim3(NT), 0, s, support, ld_support, item_row, item_e0, item_e1,
+                           item_slot, col, inv_deg, grp, att, D, bias, out, ld_out, partial, C, slope, normalize);
+        if (n_split > 0)
+            hipLaunchKernelGGL(csr_finish<NV.value>, dim3(n_split), dim3(NT), 0, s, split_row, split_slot0, split_n, partial, out, ld_out,
+                               C, slope, normalize);
+    });
     HGR_CHECK_LAUNCH("hgr_csr_group_aggregate");
     return HGR_OK;
 }

@@ -236,16 +236,13 @@ extern "C" int hgr_csr_group_att_grad(const float *support, int64_t ld_support, 
     HGR_REQUIRE(n_split == 0 || (split_row && split_slot0 && split_n && partial), "hgr_csr_group_att_grad: split rows need their tables and the partial buffer");
     hipStream_t s = (hipStream_t)stream;
     const int nv = (C + 4 * NT - 1) / (4 * NT);
-#define HGR_DGP_LAUNCH(NV)                                                                                                          \
-    do {                                                                                                                            \
-        hipLaunchKernelGGL(csr_att_grad<NV>, dim3(n_items), dim3(NT), 0, s, support, ld_support, bias, g, ld_g, y, ld_y, dout,      \
-                           ld_dout, item_row, item_e0, item_e1, item_slot, col, inv_deg, grp, D, P, partial, C, slope);             \
-        if (n_split > 0)                                                                                                            \
-            hipLaunchKernelGGL(csr_att_grad_finish<NV>, dim3(n_split), dim3(NT), 0, s, split_row, split_slot0, split_n, partial, P, \
-                               D, g, ld_g, y, ld_y, dout, ld_dout, C, slope);                                                       \
-    } while (0)
-    HGR_NV_LADDER(nv, HGR_DGP_LAUNCH);
-#undef HGR_DGP_LAUNCH
+    hgr_by_nv4(nv, [&](auto NV) {
+        hipLaunchKernelGGL(csr_att_grad<NV.value>, dim3(n_items), dim3(NT), 0, s, support, ld_support, bias, g, ld_g, y, ld_y, dout,
+                           ld_dout, item_row, item_e0, item_e1, item_slot, col, inv_deg, grp, D, P, partial, C, slope);
+        if (n_split > 0)
+            hipLaunchKernelGGL(csr_att_grad_finish<NV.value>, dim3(n_split), dim3(NT), 0, s, split_row, split_slot0, split_n, partial, P,
+                               D, g, ld_g, y, ld_y, dout, ld_dout, C, slope);
+    });
     HGR_CHECK_LAUNCH("hgr_csr_group_att_grad");
     return HGR_OK;
 }
@@ -262,9 +259,7 @@ extern "C" int hgr_dgp_loss_head(const float *O, int64_t ld_o, const int *rows, 
     if (hipMemset2DAsync(dout, (size_t)ld_dout * sizeof(float), 0, (size_t)C * sizeof(float), (size_t)n, s) != hipSuccess)
         return hgr_set_error(HGR_ELAUNCH, "hgr_dgp_loss_head: clearing dout failed");
     const int nv = (C + 4 * NT - 1) / (4 * NT);
-#define HGR_DGP_LAUNCH(NV) hipLaunchKernelGGL(loss_head<NV>, dim3(n_t), dim3(NT), 0, s, O, ld_o, rows, F, ld_f, n_t, loss_rows, dout, ld_dout, C)
-    HGR_NV_LADDER(nv, HGR_DGP_LAUNCH);
-#undef HGR_DGP_LAUNCH
+    hgr_by_nv4(nv, [&](auto NV) { hipLaunchKernelGGL(loss_head<NV.value>, dim3(n_t), dim3(NT), 0, s, O, ld_o, rows, F, ld_f, n_t, loss_rows, dout, ld_dout, C); });
     hipLaunchKernelGGL(loss_sum, dim3(1), dim3(NT), 0, s, loss_rows, n_t, loss);
     HGR_CHECK_LAUNCH("hgr_dgp_loss_head");
     return HGR_OK;

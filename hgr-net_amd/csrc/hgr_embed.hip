@@ -1,7 +1,7 @@
 // Input-side gathers: ViT patch extraction (im2col for the kernel = stride conv), text token
 // embedding and the EOT position.  All HBM-bound; reads and writes are coalesced 16-byte accesses
 // where the shapes allow it.
-#include "hgr_common.h"
+#include "hgr_launch.h"
 
 namespace {
 
@@ -163,15 +163,15 @@ extern "C" int hgr_im2col_patches_ex(const float *image, void *out, int B, int R
     if (P % 8 == 0) {
         const int64_t total = (int64_t)B * 3 * R * (R / 8);
         const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((im2col_vec8<HGR_BF16>), dim3(blocks), dim3(256), 0, s, image, (__bf16 *)out, B, R, P, Kp, rpi, roff);
-        else hipLaunchKernelGGL((im2col_vec8<HGR_F16>), dim3(blocks), dim3(256), 0, s, image, (_Float16 *)out, B, R, P, Kp, rpi, roff);
+        hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+            hipLaunchKernelGGL((im2col_vec8<dt.value>), dim3(blocks), dim3(256), 0, s, image, (E *)out, B, R, P, Kp, rpi, roff); });
     }
     const int kfirst = (P % 8 == 0) ? K : 0;     // scalar kernel: everything, or just the zero padding
     if (Kp > kfirst) {
         const int64_t total = (int64_t)B * g * g * (Kp - kfirst);
         const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((im2col_scalar<HGR_BF16>), dim3(blocks), dim3(256), 0, s, image, (__bf16 *)out, B, R, P, Kp, kfirst, rpi, roff);
-        else hipLaunchKernelGGL((im2col_scalar<HGR_F16>), dim3(blocks), dim3(256), 0, s, image, (_Float16 *)out, B, R, P, Kp, kfirst, rpi, roff);
+        hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+            hipLaunchKernelGGL((im2col_scalar<dt.value>), dim3(blocks), dim3(256), 0, s, image, (E *)out, B, R, P, Kp, kfirst, rpi, roff); });
     }
     HGR_CHECK_LAUNCH("hgr_im2col_patches");
     return HGR_OK;
@@ -209,8 +209,8 @@ extern "C" int hgr_im2col_patches_u8(const unsigned char *image, void *out, int 
     for (int c = 0; c < 3; ++c) { a[c] = 1.0f / (255.0f * std3[c]); b[c] = -mean3[c] / std3[c]; }      // host pointers
     const int64_t total = (int64_t)B * R * (R / 4);
     const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((im2col_u8<HGR_BF16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, image, (__bf16 *)out, B, R, P, Kp, rows_per_image, row_offset, a[0], a[1], a[2], b[0], b[1], b[2]);
-    else hipLaunchKernelGGL((im2col_u8<HGR_F16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, image, (_Float16 *)out, B, R, P, Kp, rows_per_image, row_offset, a[0], a[1], a[2], b[0], b[1], b[2]);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((im2col_u8<dt.value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, image, (E *)out, B, R, P, Kp, rows_per_image, row_offset, a[0], a[1], a[2], b[0], b[1], b[2]); });
     HGR_CHECK_LAUNCH("hgr_im2col_patches_u8");
     return HGR_OK;
 }

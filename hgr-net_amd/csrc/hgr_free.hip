@@ -294,30 +294,18 @@ __global__ __launch_bounds__(NT) void adam_l2_cast16(float *__restrict__ p, cons
     }
 }
 
-unsigned grid_for(int64_t items) {
-    int64_t blocks = (items + NT - 1) / NT;
-    const int64_t cap = (int64_t)hgr_cu_count() * 16;
-    return (unsigned)(blocks < 1 ? 1 : blocks > cap ? cap : blocks);
-}
-
 bool out_ok(const void *y, int64_t ld, int C) {
     return y && ld % 8 == 0 && ld >= C && hgr_aligned(y, 16);
 }
 
 #define HGR_OT_OK(name) HGR_REQUIRE(out_type == HGR_BF16 || out_type == HGR_F16 || out_type == OUT_F32, name ": out_type must be HGR_BF16, HGR_F16 or 2 (fp32)")
-#define HGR_OT_LAUNCH(kernel, ...)                                                                  \
-    do {                                                                                            \
-        if (out_type == HGR_BF16) hipLaunchKernelGGL((kernel<HGR_BF16>), __VA_ARGS__);              \
-        else if (out_type == HGR_F16) hipLaunchKernelGGL((kernel<HGR_F16>), __VA_ARGS__);           \
-        else hipLaunchKernelGGL((kernel<OUT_F32>), __VA_ARGS__);                                    \
-    } while (0)
 
 }  // namespace
 
 extern "C" int hgr_normal_counter(float *z, int64_t ld_z, uint32_t *bits, int rows, int C, int seed, int stream_id, int64_t row0, void *stream) {
     HGR_REQUIRE(z && rows >= 1 && C >= 4 && C % 4 == 0 && row0 >= 0, "hgr_normal_counter: bad arguments (C=%d must be a multiple of 4, row0 >= 0)", C);
     HGR_REQUIRE(rows_f32_ok(z, ld_z, C) && hgr_aligned(bits, 16), "hgr_normal_counter: z / bits must be 16-byte aligned, ld_z a multiple of 4 and >= C");
-    hipLaunchKernelGGL(normal_counter, dim3(grid_for((int64_t)rows * (C / 4))), dim3(NT), 0, (hipStream_t)stream, z, ld_z, (unsigned *)bits, rows, C,
+    hipLaunchKernelGGL(normal_counter, dim3(hgr_grid1((int64_t)rows * (C / 4), hgr_cu_count() * 16, NT)), dim3(NT), 0, (hipStream_t)stream, z, ld_z, (unsigned *)bits, rows, C,
                        normal_key(seed, stream_id), row0);
     HGR_CHECK_LAUNCH("hgr_normal_counter");
     return HGR_OK;
@@ -333,9 +321,10 @@ extern "C" int hgr_free_gen_input(void *out, int64_t ld_out, int out_type, const
     HGR_REQUIRE(nz >= 8 && nz % 8 == 0 && A >= 8 && A % 8 == 0, "hgr_free_gen_input: nz=%d and A=%d must be multiples of 8", nz, A);
     HGR_REQUIRE(out_ok(out, ld_out, nz + A) && rows_f32_ok(att, ld_att, A) && (!z || rows_f32_ok(z, ld_z, nz)),
                 "hgr_free_gen_input: out / att / z must be 16-byte aligned, ld_out a multiple of 8 and >= nz + A, ld_att / ld_z multiples of 4 and >= A / nz");
-    const dim3 grid(grid_for((int64_t)rows * ((nz + A) / 8))), block(NT);
-    HGR_OT_LAUNCH(gen_input, grid, block, 0, (hipStream_t)stream, out, ld_out, z, ld_z, att, ld_att, att_rows, classes, n_classes, num, rows, nz, A,
-                  normal_key(seed, stream_id), row0);
+    const dim3 grid(hgr_grid1((int64_t)rows * ((nz + A) / 8), hgr_cu_count() * 16, NT)), block(NT);
+    hgr_by_out_type(out_type, [&](auto ot) {
+        hipLaunchKernelGGL((gen_input<ot.value>), grid, block, 0, (hipStream_t)stream, out, ld_out, z, ld_z, att, ld_att, att_rows, classes, n_classes, num, rows, nz, A,
+                           normal_key(seed, stream_id), row0); });
     HGR_CHECK_LAUNCH("hgr_free_gen_input");
     return HGR_OK;
 }
@@ -349,14 +338,10 @@ extern "C" int hgr_bias_act_rows(const float *x, int64_t ld_x, const float *bias
     HGR_REQUIRE(rows_f32_ok(x, ld_x, C) && hgr_aligned(bias, 16) && out_ok(y, ld_y, 0) && ld_y >= col0 + C,
                 "hgr_bias_act_rows: x / bias / y must be 16-byte aligned, ld_x a multiple of 4 and >= C, ld_y a multiple of 8 and >= col0 + C");
     void *yo = out_type == OUT_F32 ? (void *)((float *)y + col0) : (void *)((unsigned short *)y + col0);
-    const dim3 grid(grid_for((int64_t)rows * (C / 8))), block(NT);
+    const dim3 grid(hgr_grid1((int64_t)rows * (C / 8), hgr_cu_count() * 16, NT)), block(NT);
     hipStream_t s = (hipStream_t)stream;
-#define HGR_BA(OT) do { if (act == HGR_ACT_LRELU02) hipLaunchKernelGGL((bias_act_rows<OT, 0>), grid, block, 0, s, x, ld_x, bias, yo, ld_y, rows, C); \
-                        else hipLaunchKernelGGL((bias_act_rows<OT, 1>), grid, block, 0, s, x, ld_x, bias, yo, ld_y, rows, C); } while (0)
-    if (out_type == HGR_BF16) HGR_BA(HGR_BF16);
-    else if (out_type == HGR_F16) HGR_BA(HGR_F16);
-    else HGR_BA(OUT_F32);
-#undef HGR_BA
+    hgr_by_out_type(out_type, [&](auto ot) { hgr_by_flag(act == HGR_ACT_LRELU02, [&](auto lrelu) { constexpr int ACT = lrelu.value ? 0 : 1;
+        hipLaunchKernelGGL((bias_act_rows<ot.value, ACT>), grid, block, 0, s, x, ld_x, bias, yo, ld_y, rows, C); }); });
     HGR_CHECK_LAUNCH("hgr_bias_act_rows");
     return HGR_OK;
 }
@@ -371,9 +356,10 @@ extern "C" int hgr_free_fr_tail(const float *lantent, int64_t ld_l, const float 
                 out_ok(y, ld_y, 0) && ld_y >= col0 + A,
                 "hgr_free_fr_tail: operands must be 16-byte aligned, ld_l / ld_eps / ld_mus multiples of 4 and >= 2A / A / A, ld_y a multiple of 8 and >= col0 + A");
     void *yo = out_type == OUT_F32 ? (void *)((float *)y + col0) : (void *)((unsigned short *)y + col0);
-    const dim3 grid(grid_for((int64_t)rows * (A / 8))), block(NT);
-    HGR_OT_LAUNCH(fr_tail, grid, block, 0, (hipStream_t)stream, lantent, ld_l, bias, eps, ld_eps, yo, ld_y, mus, ld_mus, rows, A,
-                  normal_key(seed, stream_id), row0);
+    const dim3 grid(hgr_grid1((int64_t)rows * (A / 8), hgr_cu_count() * 16, NT)), block(NT);
+    hgr_by_out_type(out_type, [&](auto ot) {
+        hipLaunchKernelGGL((fr_tail<ot.value>), grid, block, 0, (hipStream_t)stream, lantent, ld_l, bias, eps, ld_eps, yo, ld_y, mus, ld_mus, rows, A,
+                           normal_key(seed, stream_id), row0); });
     HGR_CHECK_LAUNCH("hgr_free_fr_tail");
     return HGR_OK;
 }
@@ -391,19 +377,15 @@ extern "C" int hgr_nll_rows16(const float *logits, int64_t ld, const int32_t *la
     const int npad = (n + 7) & ~7;
     const dim3 grid(rows), block(NT);
     hipStream_t s = (hipStream_t)stream;
-    if (npad <= NLL_RES) {
-        const size_t bytes = (size_t)npad * sizeof(float);
-        if (bytes > 65536) {                        // asked for at every such launch: the grant belongs to the current device's copy of the kernel
-            const void *k = dtype == HGR_BF16 ? (const void *)nll_rows16<HGR_BF16, true> : (const void *)nll_rows16<HGR_F16, true>;
-            hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, NLL_RES * (int)sizeof(float));
-            if (e != hipSuccess) return hgr_set_error(HGR_ELAUNCH, "hgr_nll_rows16: cannot reserve %d B of LDS: %s", NLL_RES * 4, hipGetErrorString(e));
-        }
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((nll_rows16<HGR_BF16, true>), grid, block, bytes, s, logits, ld, labels, n, loss_rows, (__bf16 *)dlogits, ld_d, (int)ld, logsm, ld_ls);
-        else hipLaunchKernelGGL((nll_rows16<HGR_F16, true>), grid, block, bytes, s, logits, ld, labels, n, loss_rows, (_Float16 *)dlogits, ld_d, (int)ld, logsm, ld_ls);
-    } else {
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((nll_rows16<HGR_BF16, false>), grid, block, 0, s, logits, ld, labels, n, loss_rows, (__bf16 *)dlogits, ld_d, (int)ld, logsm, ld_ls);
-        else hipLaunchKernelGGL((nll_rows16<HGR_F16, false>), grid, block, 0, s, logits, ld, labels, n, loss_rows, (_Float16 *)dlogits, ld_d, (int)ld, logsm, ld_ls);
+    const bool resident = npad <= NLL_RES;
+    const size_t bytes = resident ? (size_t)npad * sizeof(float) : 0;
+    if (bytes > 65536) {                            // asked for at every such launch: the grant belongs to the current device's copy of the kernel
+        const void *k = dtype == HGR_BF16 ? (const void *)nll_rows16<HGR_BF16, true> : (const void *)nll_rows16<HGR_F16, true>;
+        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, NLL_RES * (int)sizeof(float));
+        if (e != hipSuccess) return hgr_set_error(HGR_ELAUNCH, "hgr_nll_rows16: cannot reserve %d B of LDS: %s", NLL_RES * 4, hipGetErrorString(e));
     }
+    hgr_by_flag(resident, [&](auto res) { hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((nll_rows16<dt.value, res.value>), grid, block, bytes, s, logits, ld, labels, n, loss_rows, (E *)dlogits, ld_d, (int)ld, logsm, ld_ls); }); });
     HGR_CHECK_LAUNCH("hgr_nll_rows16");
     return HGR_OK;
 }
@@ -417,11 +399,11 @@ extern "C" int hgr_adam_l2_cast16(float *p, const float *g, int64_t slice_stride
     HGR_REQUIRE(hgr_aligned(p, 16) && hgr_aligned(g, 16) && hgr_aligned(m, 16) && hgr_aligned(v, 16) && hgr_aligned(w16, 8),
                 "hgr_adam_l2_cast16: p / g / m / v must be 16-byte aligned, w16 8-byte aligned");
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    const dim3 grid(grid_for(n / 4)), block(NT);
+    const dim3 grid(hgr_grid1(n / 4, hgr_cu_count() * 16, NT)), block(NT);
     hipStream_t s = (hipStream_t)stream;
     const float step_size = (float)((double)lr / bc1), isb = (float)(1.0 / sqrt(bc2));
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((adam_l2_cast16<HGR_BF16>), grid, block, 0, s, p, g, slice_stride, n_slices, alpha, m, v, (__bf16 *)w16, n / 4, beta1, beta2, eps, wd, step_size, isb);
-    else hipLaunchKernelGGL((adam_l2_cast16<HGR_F16>), grid, block, 0, s, p, g, slice_stride, n_slices, alpha, m, v, (_Float16 *)w16, n / 4, beta1, beta2, eps, wd, step_size, isb);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((adam_l2_cast16<dt.value>), grid, block, 0, s, p, g, slice_stride, n_slices, alpha, m, v, (E *)w16, n / 4, beta1, beta2, eps, wd, step_size, isb); });
     HGR_CHECK_LAUNCH("hgr_adam_l2_cast16");
     return HGR_OK;
 }

@@ -3,6 +3,7 @@
 // Loop: issue stage t+1, compute stage t, vmcnt(0) + one barrier per K-tile ("minimum 2-phase").  Also the implicit-GEMM 3x3
 // convolution (CONV), the 256 x 64 arrangement for narrow outputs (TALL) and the one-stage K = 64 variant (ONEK).
 #include "hgr_gemm_common.h"
+#include "hgr_launch.h"
 
 namespace hgr_gemm {
 
@@ -315,8 +316,7 @@ void plain_epi(const GemmArgs &a, bool out32, dim3 grid, hipStream_t s) {
     if constexpr (EPI == HGR_EPI_QGELU_GRAD16 || EPI == HGR_EPI_BIAS_ADD16_RELU) {      // 16-bit output only (checked by the host entry)
         hipLaunchKernelGGL((gemm_nt_128<DT, EPI, false>), grid, dim3(NT), 0, s, a);
     } else {
-        if (out32) hipLaunchKernelGGL((gemm_nt_128<DT, EPI, true>), grid, dim3(NT), 0, s, a);
-        else hipLaunchKernelGGL((gemm_nt_128<DT, EPI, false>), grid, dim3(NT), 0, s, a);
+        hgr_by_flag(out32, [&](auto o32) { hipLaunchKernelGGL((gemm_nt_128<DT, EPI, o32.value>), grid, dim3(NT), 0, s, a); });
     }
 }
 
@@ -351,8 +351,7 @@ void launch_128_dt(const GemmArgs &a, int epi, bool out32, int variant, dim3 gri
 }  // namespace
 
 void launch_128(const GemmArgs &a, int dtype, int epi, bool out32, int variant, dim3 grid, hipStream_t s) {
-    if (dtype == HGR_BF16) launch_128_dt<HGR_BF16>(a, epi, out32, variant, grid, s);
-    else launch_128_dt<HGR_F16>(a, epi, out32, variant, grid, s);
+    hgr_by_dtype(dtype, [&](auto dt) { launch_128_dt<dt.value>(a, epi, out32, variant, grid, s); });
 }
 
 }  // namespace hgr_gemm

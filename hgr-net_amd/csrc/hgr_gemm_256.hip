@@ -24,6 +24,7 @@
 // "Pipelining across barriers", counted vmcnt + raw s_barrier, all LDS in one array.)
 // =================================================================================================
 #include "hgr_gemm_common.h"
+#include "hgr_launch.h"
 
 namespace hgr_gemm {
 
@@ -368,8 +369,7 @@ void plain256(const GemmArgs &a, bool out32, dim3 grid, hipStream_t s) {
     if constexpr (EPI == HGR_EPI_QGELU_GRAD16 || EPI == HGR_EPI_BIAS_ADD16_RELU) {
         hipLaunchKernelGGL((gemm_nt_256<DT, EPI, false>), grid, dim3(NT256), 0, s, a);
     } else {
-        if (out32) hipLaunchKernelGGL((gemm_nt_256<DT, EPI, true>), grid, dim3(NT256), 0, s, a);
-        else hipLaunchKernelGGL((gemm_nt_256<DT, EPI, false>), grid, dim3(NT256), 0, s, a);
+        hgr_by_flag(out32, [&](auto o32) { hipLaunchKernelGGL((gemm_nt_256<DT, EPI, o32.value>), grid, dim3(NT256), 0, s, a); });
     }
 }
 template <int DT>
@@ -389,8 +389,7 @@ void launch_256_dt(const GemmArgs &a, int epi, bool out32, bool conv, dim3 grid,
 }  // namespace
 
 void launch_256(const GemmArgs &a, int dtype, int epi, bool out32, bool conv, dim3 grid, hipStream_t s) {
-    if (dtype == HGR_BF16) launch_256_dt<HGR_BF16>(a, epi, out32, conv, grid, s);
-    else launch_256_dt<HGR_F16>(a, epi, out32, conv, grid, s);
+    hgr_by_dtype(dtype, [&](auto dt) { launch_256_dt<dt.value>(a, epi, out32, conv, grid, s); });
 }
 
 }  // namespace hgr_gemm

@@ -22,6 +22,7 @@
 // 3 phases ahead; if a piece is late the partner workgroup's MFMAs fill the gap.
 // =================================================================================================
 #include "hgr_gemm_common.h"
+#include "hgr_launch.h"
 
 namespace hgr_gemm {
 
@@ -949,25 +950,22 @@ void launch_duo_dt(const GemmArgs &a, int epi, bool out32, int ln, dim3 grid, hi
         case 5: hipLaunchKernelGGL((gemm_nt_duo<DT, HGR_EPI_BIAS_RELU, false, 0, true>), grid, dim3(NTD), 0, s, a); return;   // 3 x 3 convolution (implicit im2col loader)
         default: break;
     }
-#define HGR_DUO(E) do { if (out32) hipLaunchKernelGGL((gemm_nt_duo<DT, E, true>), grid, dim3(NTD), 0, s, a); \
-                        else hipLaunchKernelGGL((gemm_nt_duo<DT, E, false>), grid, dim3(NTD), 0, s, a); } while (0)
+    auto plain = [&](auto e) { hgr_by_flag(out32, [&](auto o32) { hipLaunchKernelGGL((gemm_nt_duo<DT, e.value, o32.value>), grid, dim3(NTD), 0, s, a); }); };
     switch (epi) {
-        case HGR_EPI_NONE: HGR_DUO(HGR_EPI_NONE); break;
-        case HGR_EPI_BIAS: HGR_DUO(HGR_EPI_BIAS); break;
-        case HGR_EPI_BIAS_QUICKGELU: HGR_DUO(HGR_EPI_BIAS_QUICKGELU); break;
-        case HGR_EPI_BIAS_RELU: HGR_DUO(HGR_EPI_BIAS_RELU); break;
+        case HGR_EPI_NONE: plain(hgr_int<HGR_EPI_NONE>{}); break;
+        case HGR_EPI_BIAS: plain(hgr_int<HGR_EPI_BIAS>{}); break;
+        case HGR_EPI_BIAS_QUICKGELU: plain(hgr_int<HGR_EPI_BIAS_QUICKGELU>{}); break;
+        case HGR_EPI_BIAS_RELU: plain(hgr_int<HGR_EPI_BIAS_RELU>{}); break;
         case HGR_EPI_BIAS_ADD16_RELU: hipLaunchKernelGGL((gemm_nt_duo<DT, HGR_EPI_BIAS_ADD16_RELU, false>), grid, dim3(NTD), 0, s, a); break;
         case HGR_EPI_ACCUM: hipLaunchKernelGGL((gemm_nt_duo<DT, HGR_EPI_ACCUM, true>), grid, dim3(NTD), 0, s, a); break;
         case HGR_EPI_QGELU_GRAD16: hipLaunchKernelGGL((gemm_nt_duo<DT, HGR_EPI_QGELU_GRAD16, false>), grid, dim3(NTD), 0, s, a); break;
         default: hipLaunchKernelGGL((gemm_nt_duo<DT, HGR_EPI_BIAS_RESIDUAL, true>), grid, dim3(NTD), 0, s, a); break;
     }
-#undef HGR_DUO
 }
 }  // namespace
 
 void launch_duo(const GemmArgs &a, int dtype, int epi, bool out32, int ln, dim3 grid, hipStream_t s) {
-    if (dtype == HGR_BF16) launch_duo_dt<HGR_BF16>(a, epi, out32, ln, grid, s);
-    else launch_duo_dt<HGR_F16>(a, epi, out32, ln, grid, s);
+    hgr_by_dtype(dtype, [&](auto dt) { launch_duo_dt<dt.value>(a, epi, out32, ln, grid, s); });
 }
 
 }  // namespace hgr_gemm

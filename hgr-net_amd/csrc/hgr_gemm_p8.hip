@@ -27,6 +27,7 @@
 // global loads - row statistics, ln_s / ln_c of the tile's 256 columns, parked in LDS - retire before those DMAs are issued.
 // =================================================================================================
 #include "hgr_gemm_common.h"
+#include "hgr_launch.h"
 
 namespace hgr_gemm {
 namespace {
@@ -210,13 +211,7 @@ bool p8_covers(int M, int N, int K) {
 // the caller planned the launch (plan_p8, hgr_gemm.hip: whole tiles, at most one workgroup per CU)
 void launch_p8(const GemmArgs &a, int dtype, int act, dim3 grid, hipStream_t s) {
     const dim3 block(P8_NT);
-    if (dtype == HGR_BF16) {
-        if (act) hipLaunchKernelGGL((gemm_nt_p8<HGR_BF16, 1>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((gemm_nt_p8<HGR_BF16, 0>), grid, block, 0, s, a);
-    } else {
-        if (act) hipLaunchKernelGGL((gemm_nt_p8<HGR_F16, 1>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((gemm_nt_p8<HGR_F16, 0>), grid, block, 0, s, a);
-    }
+    hgr_by_dtype(dtype, [&](auto dt) { hgr_by_flag(act, [&](auto gelu) { hipLaunchKernelGGL((gemm_nt_p8<dt.value, gelu.value>), grid, block, 0, s, a); }); });
 }
 
 }  // namespace hgr_gemm

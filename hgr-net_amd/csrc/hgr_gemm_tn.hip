@@ -20,6 +20,7 @@
 // LDS stages (64 KB), blockIdx.y = reduction slice.  EXEC is all ones at every transposing read (no divergent code
 // around them), as the ISA requires.
 #include "hgr_gemm_common.h"
+#include "hgr_launch.h"
 #include <stdlib.h>
 
 #pragma clang diagnostic ignored "-Winline-asm"   // the LDS-DMA assembly below names m0 as clobbered (reserved register: hipcc warns)
@@ -342,19 +343,12 @@ int tn_launch(const void *P, int64_t ldp, const void *Q, int64_t ldq, float *par
     if (!conv && tn_tile(Na, Nb) == 256) {
         a.tiles_b = (Nb + 255) / 256;
         dim3 grid256((unsigned)(((Na + 255) / 256) * a.tiles_b * S));
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((gemm_tn_256<HGR_BF16>), grid256, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((gemm_tn_256<HGR_F16>), grid256, dim3(512), 0, s, a);
+        hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((gemm_tn_256<dt.value>), grid256, dim3(512), 0, s, a); });
         HGR_CHECK_LAUNCH(name);
         return HGR_OK;
     }
     dim3 grid((unsigned)(((Na + 127) / 128) * a.tiles_b), (unsigned)S);
-    if (conv) {
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((gemm_tn_128<HGR_BF16, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gemm_tn_128<HGR_F16, true>), grid, dim3(256), 0, s, a);
-    } else {
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((gemm_tn_128<HGR_BF16, false>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gemm_tn_128<HGR_F16, false>), grid, dim3(256), 0, s, a);
-    }
+    hgr_by_flag(conv, [&](auto cv) { hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((gemm_tn_128<dt.value, cv.value>), grid, dim3(256), 0, s, a); }); });
     HGR_CHECK_LAUNCH(name);
     return HGR_OK;
 }

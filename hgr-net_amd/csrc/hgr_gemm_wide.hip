@@ -30,6 +30,7 @@
 // slots (n tiles 0-3 and 4-7); inside a slot the values are paired exactly as in gemm_nt_duo, where a wave's 64 columns are one slot.
 // =================================================================================================
 #include "hgr_gemm_common.h"
+#include "hgr_launch.h"
 
 namespace hgr_gemm {
 namespace {
@@ -213,8 +214,7 @@ extern "C" int hgr_gemm_nt_res_stats_wide(const void *A, int64_t lda, const void
     a.ln_flag = flag; a.ln_guard = guard_sumsq;
     a.tiles_m = M / WD_BM; a.tiles_n = N / WD_BN;
     const dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(WD_NT);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((gemm_nt_res_wide<HGR_BF16>), grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((gemm_nt_res_wide<HGR_F16>), grid, block, 0, (hipStream_t)stream, a);
+    hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((gemm_nt_res_wide<dt.value>), grid, block, 0, (hipStream_t)stream, a); });
     HGR_CHECK_LAUNCH("hgr_gemm_nt_res_stats_wide");
     return HGR_OK;
 }

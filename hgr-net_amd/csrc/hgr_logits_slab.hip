@@ -25,6 +25,7 @@
 // them into the level arg-max, the top-1 and the top-k.
 // =================================================================================================
 #include "hgr_gemm_common.h"
+#include "hgr_launch.h"
 
 namespace hgr_gemm {
 
@@ -262,8 +263,7 @@ __global__ __launch_bounds__(LS_NT) void logits_slab(SlabArgs p) {
 
 void launch_logits_slab(const SlabArgs &a, int dtype, hipStream_t s) {
     const dim3 grid((unsigned)(a.Np / 96), (unsigned)((a.M + 511) / 512)), block(LS_NT);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((logits_slab<HGR_BF16>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((logits_slab<HGR_F16>), grid, block, 0, s, a);
+    hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((logits_slab<dt.value>), grid, block, 0, s, a); });
 }
 
 }  // namespace hgr_gemm

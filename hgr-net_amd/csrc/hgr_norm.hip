@@ -5,7 +5,7 @@
 // (float4 per lane, up to 16 per lane = 4096 columns), loads and stores are 16-byte (8-byte for the
 // 16-bit outputs) and coalesced, statistics are two-pass (mean, then centred second moment) like
 // torch's LayerNorm, reduced with wave shuffles.  4 rows per 256-thread block.
-#include "hgr_common.h"
+#include "hgr_launch.h"
 
 namespace {
 
@@ -273,15 +273,10 @@ extern "C" int hgr_layernorm(const float *x, const float *gamma, const float *be
     HGR_REQUIRE(row_mul >= 1, "hgr_layernorm: row_mul must be >= 1");
     dim3 grid((rows + 3) / 4), block(256);
     hipStream_t s = (hipStream_t)stream;
-#define HGR_LN(NVV)                                                                                                          \
-    do {                                                                                                                     \
-        if (out_f32) hipLaunchKernelGGL((layernorm_rows<HGR_BF16, true, NVV>), grid, block, 0, s, x, gamma, beta, y, rows, W, row_mul, row_idx, eps); \
-        else if (dtype == HGR_BF16) hipLaunchKernelGGL((layernorm_rows<HGR_BF16, false, NVV>), grid, block, 0, s, x, gamma, beta, y, rows, W, row_mul, row_idx, eps); \
-        else hipLaunchKernelGGL((layernorm_rows<HGR_F16, false, NVV>), grid, block, 0, s, x, gamma, beta, y, rows, W, row_mul, row_idx, eps); \
-    } while (0)
-    const int nvl = (W / 4 + 63) / 64;
-    if (nvl <= 1) HGR_LN(1); else if (nvl <= 2) HGR_LN(2); else if (nvl <= 4) HGR_LN(4); else if (nvl <= 8) HGR_LN(8); else HGR_LN(16);
-#undef HGR_LN
+    hgr_by_nv_pow2((W / 4 + 63) / 64, [&](auto nv) {         // fp32 output has one instantiation, under HGR_BF16, whatever dtype says
+        if (out_f32) hipLaunchKernelGGL((layernorm_rows<HGR_BF16, true, nv.value>), grid, block, 0, s, x, gamma, beta, y, rows, W, row_mul, row_idx, eps);
+        else hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((layernorm_rows<dt.value, false, nv.value>), grid, block, 0, s, x, gamma, beta, y, rows, W, row_mul, row_idx, eps); });
+    });
     HGR_CHECK_LAUNCH("hgr_layernorm");
     return HGR_OK;
 }
@@ -293,10 +288,8 @@ extern "C" int hgr_vit_embed_ln(const float *patches, const float *class_embeddi
     HGR_REQUIRE(hgr_aligned(patches, 16) && hgr_aligned(class_embedding, 16) && hgr_aligned(positional_embedding, 16) &&
                 hgr_aligned(gamma, 16) && hgr_aligned(beta, 16) && hgr_aligned(x, 16), "hgr_vit_embed_ln: operands must be 16-byte aligned");
     const int rows = B * (G + 1);
-#define HGR_VE(NVV) hipLaunchKernelGGL((vit_embed_ln<NVV>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, patches, class_embedding, positional_embedding, gamma, beta, x, B, G, W, eps)
-    const int nvl = (W / 4 + 63) / 64;
-    if (nvl <= 1) HGR_VE(1); else if (nvl <= 2) HGR_VE(2); else if (nvl <= 4) HGR_VE(4); else if (nvl <= 8) HGR_VE(8); else HGR_VE(16);
-#undef HGR_VE
+    hgr_by_nv_pow2((W / 4 + 63) / 64, [&](auto nv) {
+        hipLaunchKernelGGL((vit_embed_ln<nv.value>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, patches, class_embedding, positional_embedding, gamma, beta, x, B, G, W, eps); });
     HGR_CHECK_LAUNCH("hgr_vit_embed_ln");
     return HGR_OK;
 }
@@ -307,14 +300,8 @@ extern "C" int hgr_l2norm_rows(const float *x, void *y16, float *y32, int rows, 
     HGR_REQUIRE(hgr_aligned(x, 16) && hgr_aligned(y16, 8) && hgr_aligned(y32, 16), "hgr_l2norm_rows: misaligned operand");
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_l2norm_rows: bad dtype %d", dtype);
     dim3 grid((rows + 3) / 4), block(256);
-#define HGR_L2(NVV)                                                                                                    \
-    do {                                                                                                               \
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((l2norm_rows<HGR_BF16, NVV>), grid, block, 0, (hipStream_t)stream, x, y16, y32, rows, D); \
-        else hipLaunchKernelGGL((l2norm_rows<HGR_F16, NVV>), grid, block, 0, (hipStream_t)stream, x, y16, y32, rows, D); \
-    } while (0)
-    const int nvl = (D / 4 + 63) / 64;
-    if (nvl <= 1) HGR_L2(1); else if (nvl <= 2) HGR_L2(2); else if (nvl <= 4) HGR_L2(4); else if (nvl <= 8) HGR_L2(8); else HGR_L2(16);
-#undef HGR_L2
+    hgr_by_nv_pow2((D / 4 + 63) / 64, [&](auto nv) { hgr_by_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((l2norm_rows<dt.value, nv.value>), grid, block, 0, (hipStream_t)stream, x, y16, y32, rows, D); }); });
     HGR_CHECK_LAUNCH("hgr_l2norm_rows");
     return HGR_OK;
 }
@@ -331,12 +318,8 @@ extern "C" int hgr_vit_embed_ln_stats(const float *patches, const float *class_e
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_vit_embed_ln_stats: bad dtype %d", dtype);
     const int rows = B * (G + 1);
     float *nox = nullptr;
-#define HGR_VE(NVV) do { \
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((vit_embed_ln<NVV, HGR_BF16, true>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, patches, class_embedding, positional_embedding, gamma, beta, nox, B, G, W, eps, xh, xl, stats); \
-        else hipLaunchKernelGGL((vit_embed_ln<NVV, HGR_F16, true>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, patches, class_embedding, positional_embedding, gamma, beta, nox, B, G, W, eps, xh, xl, stats); } while (0)
-    const int nvl = (W / 4 + 63) / 64;
-    if (nvl <= 1) HGR_VE(1); else if (nvl <= 2) HGR_VE(2); else if (nvl <= 4) HGR_VE(4); else if (nvl <= 8) HGR_VE(8); else HGR_VE(16);
-#undef HGR_VE
+    hgr_by_nv_pow2((W / 4 + 63) / 64, [&](auto nv) { hgr_by_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((vit_embed_ln<nv.value, dt.value, true>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, patches, class_embedding, positional_embedding, gamma, beta, nox, B, G, W, eps, xh, xl, stats); }); });
     HGR_CHECK_LAUNCH("hgr_vit_embed_ln_stats");
     return HGR_OK;
 }
@@ -346,8 +329,7 @@ extern "C" int hgr_row_stats16(const float *x, void *xh, void *xl, float *stats,
     HGR_REQUIRE(rows >= 1 && W >= 64 && W % 64 == 0, "hgr_row_stats16: rows=%d W=%d unsupported (W %% 64 == 0)", rows, W);
     HGR_REQUIRE(hgr_aligned(x, 16) && hgr_aligned(xh, 8) && hgr_aligned(xl, 8) && hgr_aligned(stats, 8), "hgr_row_stats16: misaligned operand");
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_row_stats16: bad dtype %d", dtype);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((row_stats16<HGR_BF16>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, xh, xl, stats, rows, W);
-    else hipLaunchKernelGGL((row_stats16<HGR_F16>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, xh, xl, stats, rows, W);
+    hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((row_stats16<dt.value>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, xh, xl, stats, rows, W); });
     HGR_CHECK_LAUNCH("hgr_row_stats16");
     return HGR_OK;
 }
@@ -357,8 +339,7 @@ extern "C" int hgr_pair_rows_f32(const void *xh, const void *xl, float *out, int
     HGR_REQUIRE(rows >= 1 && W >= 4 && W % 4 == 0 && row_mul >= 1, "hgr_pair_rows_f32: rows=%d W=%d row_mul=%lld unsupported", rows, W, (long long)row_mul);
     HGR_REQUIRE(hgr_aligned(xh, 8) && hgr_aligned(xl, 8) && hgr_aligned(out, 16), "hgr_pair_rows_f32: misaligned operand");
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_pair_rows_f32: bad dtype %d", dtype);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((pair_rows_f32<HGR_BF16>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, xh, xl, out, rows, W, row_mul, row_idx);
-    else hipLaunchKernelGGL((pair_rows_f32<HGR_F16>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, xh, xl, out, rows, W, row_mul, row_idx);
+    hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((pair_rows_f32<dt.value>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, xh, xl, out, rows, W, row_mul, row_idx); });
     HGR_CHECK_LAUNCH("hgr_pair_rows_f32");
     return HGR_OK;
 }
@@ -373,11 +354,8 @@ extern "C" int hgr_vit_head(const void *xh, const void *xl, int64_t ldx, int64_t
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_vit_head: bad dtype %d", dtype);
     const size_t lds = (size_t)16 * (W * 2 + 16);
     dim3 grid((unsigned)((B + 15) / 16), (unsigned)((D + 127) / 128));
-    const int nv = (W / 4 + 63) / 64;
-#define HGR_HEAD(NV) do { if (dtype == HGR_BF16) hipLaunchKernelGGL((vit_head<HGR_BF16, NV>), grid, dim3(256), lds, (hipStream_t)stream, xh, xl, ldx, row_mul, gamma, beta, eps, proj_t, out, B, W, D); \
-                          else hipLaunchKernelGGL((vit_head<HGR_F16, NV>), grid, dim3(256), lds, (hipStream_t)stream, xh, xl, ldx, row_mul, gamma, beta, eps, proj_t, out, B, W, D); } while (0)
-    if (nv <= 1) HGR_HEAD(1); else if (nv <= 2) HGR_HEAD(2); else if (nv <= 4) HGR_HEAD(4); else if (nv <= 8) HGR_HEAD(8); else HGR_HEAD(16);
-#undef HGR_HEAD
+    hgr_by_nv_pow2((W / 4 + 63) / 64, [&](auto nv) { hgr_by_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((vit_head<dt.value, nv.value>), grid, dim3(256), lds, (hipStream_t)stream, xh, xl, ldx, row_mul, gamma, beta, eps, proj_t, out, B, W, D); }); });
     HGR_CHECK_LAUNCH("hgr_vit_head");
     return HGR_OK;
 }

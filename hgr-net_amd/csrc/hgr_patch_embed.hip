@@ -34,6 +34,7 @@
 // No workgroup depends on another one.
 // =================================================================================================
 #include "hgr_gemm_common.h"
+#include "hgr_launch.h"
 
 namespace hgr_gemm {
 namespace {
@@ -259,8 +260,7 @@ extern "C" int hgr_vit_patch_embed_ln(const float *image, const void *conv_w, co
                 hgr_aligned(gamma, 16) && hgr_aligned(beta, 16) && hgr_aligned(xh, 16) && hgr_aligned(xl, 16) && hgr_aligned(stats, 16),
                 "hgr_vit_patch_embed_ln: operands must be 16-byte aligned");
     const dim3 grid((B + 1) / 2), block(PE_NT);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((vit_patch_embed_ln<HGR_BF16>), grid, block, 0, (hipStream_t)stream, image, (const char *)conv_w, class_embedding, positional_embedding, gamma, beta, xh, xl, stats, B, R, gs, eps);
-    else hipLaunchKernelGGL((vit_patch_embed_ln<HGR_F16>), grid, block, 0, (hipStream_t)stream, image, (const char *)conv_w, class_embedding, positional_embedding, gamma, beta, xh, xl, stats, B, R, gs, eps);
+    hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((vit_patch_embed_ln<dt.value>), grid, block, 0, (hipStream_t)stream, image, (const char *)conv_w, class_embedding, positional_embedding, gamma, beta, xh, xl, stats, B, R, gs, eps); });
     HGR_CHECK_LAUNCH("hgr_vit_patch_embed_ln");
     return HGR_OK;
 }

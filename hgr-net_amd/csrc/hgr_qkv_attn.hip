@@ -28,6 +28,7 @@
 // hgr_gemm_nt_ln + hgr_mha (tests/test_gpu_kernels.py::test_gemm_ln_mha_equals_gemm_then_mha).
 // =================================================================================================
 #include "hgr_gemm_common.h"
+#include "hgr_launch.h"
 
 namespace hgr_gemm {
 
@@ -446,13 +447,7 @@ void launch_qkv_attn(const QkvAttnArgs &a, int dtype, bool causal, hipStream_t s
     const int tiles = a.tiles_m * a.H;
     // (eight-XCD raster; a launch of fewer than 8 row tiles keeps the plain walk)
     const dim3 grid((unsigned)(qa_persist.get() ? (tiles < hgr_cu_count() ? tiles : hgr_cu_count()) : tiles)), block(QA_NT);
-    if (dtype == HGR_BF16) {
-        if (causal) hipLaunchKernelGGL((qkv_attn<HGR_BF16, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((qkv_attn<HGR_BF16, false>), grid, block, 0, s, a);
-    } else {
-        if (causal) hipLaunchKernelGGL((qkv_attn<HGR_F16, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((qkv_attn<HGR_F16, false>), grid, block, 0, s, a);
-    }
+    hgr_by_dtype(dtype, [&](auto dt) { hgr_by_flag(causal, [&](auto caus) { hipLaunchKernelGGL((qkv_attn<dt.value, caus.value>), grid, block, 0, s, a); }); });
 }
 
 }  // namespace hgr_gemm

@@ -1,7 +1,7 @@
 // Small streaming kernels of the ModifiedResNet tower (clip/model.py:93-150): stem im2col, 2x2 average
 // pooling, attention-pool token assembly and the single-query attention.  All HBM-bound; 16-byte
 // accesses along the channel dimension (NHWC keeps channels contiguous).
-#include "hgr_common.h"
+#include "hgr_launch.h"
 
 namespace {
 
@@ -147,8 +147,6 @@ __global__ __launch_bounds__(256) void attnpool_attend(const float *__restrict__
     out[(int64_t)b * Ew + h * 64 + lane] = (E)(o * inv);
 }
 
-unsigned grid_for(int64_t total) { return (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384); }
-
 }  // namespace
 
 
@@ -157,8 +155,8 @@ extern "C" int hgr_stem_im2col(const float *image, void *out, int B, int R, int 
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_stem_im2col: bad dtype %d", dtype);
     const int Ho = (R - 1) / 2 + 1;
     const int64_t total = (int64_t)B * Ho * Ho;
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((stem_im2col<HGR_BF16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, image, (__bf16 *)out, B, R);
-    else hipLaunchKernelGGL((stem_im2col<HGR_F16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, image, (_Float16 *)out, B, R);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((stem_im2col<dt.value>), dim3(hgr_grid1(total, 16384)), dim3(256), 0, (hipStream_t)stream, image, (E *)out, B, R); });
     HGR_CHECK_LAUNCH("hgr_stem_im2col");
     return HGR_OK;
 }
@@ -168,8 +166,8 @@ extern "C" int hgr_avgpool2_nhwc(const void *x, void *out, int B, int H, int W, 
     HGR_REQUIRE(hgr_aligned(x, 16) && hgr_aligned(out, 16), "hgr_avgpool2_nhwc: misaligned operand");
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_avgpool2_nhwc: bad dtype %d", dtype);
     const int64_t total = (int64_t)B * (H / 2) * (W / 2) * (C / 8);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((avgpool2<HGR_BF16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)x, (__bf16 *)out, B, H, W, C);
-    else hipLaunchKernelGGL((avgpool2<HGR_F16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x, (_Float16 *)out, B, H, W, C);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((avgpool2<dt.value>), dim3(hgr_grid1(total, 16384)), dim3(256), 0, (hipStream_t)stream, (const E *)x, (E *)out, B, H, W, C); });
     HGR_CHECK_LAUNCH("hgr_avgpool2_nhwc");
     return HGR_OK;
 }
@@ -179,8 +177,8 @@ extern "C" int hgr_attnpool_tokens(const void *x, const float *pos, void *out, i
     HGR_REQUIRE(hgr_aligned(x, 16) && hgr_aligned(out, 16), "hgr_attnpool_tokens: misaligned operand");
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_attnpool_tokens: bad dtype %d", dtype);
     const int64_t total = (int64_t)B * (C / 8);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((attnpool_tokens<HGR_BF16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)x, pos, (__bf16 *)out, B, S, C);
-    else hipLaunchKernelGGL((attnpool_tokens<HGR_F16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x, pos, (_Float16 *)out, B, S, C);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((attnpool_tokens<dt.value>), dim3(hgr_grid1(total, 16384)), dim3(256), 0, (hipStream_t)stream, (const E *)x, pos, (E *)out, B, S, C); });
     HGR_CHECK_LAUNCH("hgr_attnpool_tokens");
     return HGR_OK;
 }
@@ -190,8 +188,8 @@ extern "C" int hgr_attnpool_attend(const float *q, const void *k, const void *v,
     HGR_REQUIRE(hgr_aligned(k, 16) && hgr_aligned(v, 2) && hgr_aligned(q, 4), "hgr_attnpool_attend: misaligned operand");
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_attnpool_attend: bad dtype %d", dtype);
     const unsigned blocks = (unsigned)(((int64_t)B * heads + 3) / 4);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((attnpool_attend<HGR_BF16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, q, (const __bf16 *)k, (const __bf16 *)v, (__bf16 *)out, B, L, heads);
-    else hipLaunchKernelGGL((attnpool_attend<HGR_F16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, q, (const _Float16 *)k, (const _Float16 *)v, (_Float16 *)out, B, L, heads);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((attnpool_attend<dt.value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, q, (const E *)k, (const E *)v, (E *)out, B, L, heads); });
     HGR_CHECK_LAUNCH("hgr_attnpool_attend");
     return HGR_OK;
 }

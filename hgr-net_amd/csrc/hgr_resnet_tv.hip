@@ -5,11 +5,9 @@
 // Rounding contract of the stem, shared by the fused kernel and the unfused route (hgr_stem7_im2col -> hgr_gemm_nt(BIAS_RELU) ->
 // hgr_maxpool3s2_nhwc): relu(conv + bias) is rounded to 16 bit ONCE and the max is taken over those 16-bit values.  A max-pool tap outside
 // the conv map is IGNORED (never a padded 0), so the kernels stay right for inputs that are not preceded by a ReLU.
-#include "hgr_common.h"
+#include "hgr_launch.h"
 
 namespace {
-
-unsigned grid_for(int64_t total) { return (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384); }
 
 // ---- fused stem -------------------------------------------------------------------------------------------------------------------
 // A workgroup owns an 8 x 8 tile of POOLED outputs of one image = 17 x 17 conv outputs = a 39 x 40 x 3 input patch, which is converted
@@ -301,8 +299,7 @@ extern "C" int hgr_stem7_pool(const float *image, const void *w, const float *bi
     HGR_REQUIRE(ntiles < (1ll << 31), "hgr_stem7_pool: too many tiles");
     dim3 grid((unsigned)std::min<int64_t>(ntiles, 2 * (int64_t)hgr_cu_count()));     // persistent: two workgroups per compute unit
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((stem7_pool<HGR_BF16>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((stem7_pool<HGR_F16>), grid, dim3(256), 0, s, a);
+    hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((stem7_pool<dt.value>), grid, dim3(256), 0, s, a); });
     HGR_CHECK_LAUNCH("hgr_stem7_pool");
     return HGR_OK;
 }
@@ -314,8 +311,8 @@ extern "C" int hgr_stem7_im2col(const float *image, void *out, int B, int R, int
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_stem7_im2col: bad dtype %d", dtype);
     const int Hc = (R - 1) / 2 + 1;
     const int64_t total = (int64_t)B * Hc * Hc * (Kp / 8);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((stem7_im2col<HGR_BF16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, image, (__bf16 *)out, B, R, Kp);
-    else hipLaunchKernelGGL((stem7_im2col<HGR_F16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, image, (_Float16 *)out, B, R, Kp);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((stem7_im2col<dt.value>), dim3(hgr_grid1(total, 16384)), dim3(256), 0, (hipStream_t)stream, image, (E *)out, B, R, Kp); });
     HGR_CHECK_LAUNCH("hgr_stem7_im2col");
     return HGR_OK;
 }
@@ -325,8 +322,8 @@ extern "C" int hgr_maxpool3s2_nhwc(const void *x, void *out, int B, int H, int W
     HGR_REQUIRE(hgr_aligned(x, 16) && hgr_aligned(out, 16), "hgr_maxpool3s2_nhwc: misaligned operand");
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_maxpool3s2_nhwc: bad dtype %d", dtype);
     const int64_t total = (int64_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * (C / 8);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((maxpool3s2<HGR_BF16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)x, (__bf16 *)out, B, H, W, C);
-    else hipLaunchKernelGGL((maxpool3s2<HGR_F16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x, (_Float16 *)out, B, H, W, C);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((maxpool3s2<dt.value>), dim3(hgr_grid1(total, 16384)), dim3(256), 0, (hipStream_t)stream, (const E *)x, (E *)out, B, H, W, C); });
     HGR_CHECK_LAUNCH("hgr_maxpool3s2_nhwc");
     return HGR_OK;
 }
@@ -336,7 +333,7 @@ extern "C" int hgr_subsample2_nhwc(const void *x, void *out, int B, int H, int W
     HGR_REQUIRE(hgr_aligned(x, 16) && hgr_aligned(out, 16), "hgr_subsample2_nhwc: misaligned operand");
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_subsample2_nhwc: bad dtype %d", dtype);
     const int64_t total = (int64_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * (C / 8);
-    hipLaunchKernelGGL(subsample2, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const u32x4 *)x, (u32x4 *)out, B, H, W, C / 8);
+    hipLaunchKernelGGL(subsample2, dim3(hgr_grid1(total, 16384)), dim3(256), 0, (hipStream_t)stream, (const u32x4 *)x, (u32x4 *)out, B, H, W, C / 8);
     HGR_CHECK_LAUNCH("hgr_subsample2_nhwc");
     return HGR_OK;
 }
@@ -347,15 +344,10 @@ extern "C" int hgr_meanpool_nhwc(const void *x, void *out, int B, int H, int W, 
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "hgr_meanpool_nhwc: bad dtype %d", dtype);
     HGR_REQUIRE(out_f32 == 0 || out_f32 == 1, "hgr_meanpool_nhwc: out_f32=%d must be 0 or 1", out_f32);
     const int64_t total = (int64_t)B * (C / 8);
-    const dim3 grid(grid_for(total));
+    const dim3 grid(hgr_grid1(total, 16384));
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == HGR_BF16) {
-        if (out_f32) hipLaunchKernelGGL((meanpool<HGR_BF16, true>), grid, dim3(256), 0, s, (const __bf16 *)x, out, B, H * W, C);
-        else hipLaunchKernelGGL((meanpool<HGR_BF16, false>), grid, dim3(256), 0, s, (const __bf16 *)x, out, B, H * W, C);
-    } else {
-        if (out_f32) hipLaunchKernelGGL((meanpool<HGR_F16, true>), grid, dim3(256), 0, s, (const _Float16 *)x, out, B, H * W, C);
-        else hipLaunchKernelGGL((meanpool<HGR_F16, false>), grid, dim3(256), 0, s, (const _Float16 *)x, out, B, H * W, C);
-    }
+    hgr_by_dtype(dtype, [&](auto dt) { hgr_by_flag(out_f32, [&](auto f32) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((meanpool<dt.value, f32.value>), grid, dim3(256), 0, s, (const E *)x, out, B, H * W, C); }); });
     HGR_CHECK_LAUNCH("hgr_meanpool_nhwc");
     return HGR_OK;
 }

@@ -1,8 +1,9 @@
 // What the baselines' row kernels (hgr_dgp.hip, hgr_dgp_train.hip, hgr_free.hip, hgr_cnzsl.hip) share: the counter mix, the block
-// reductions of a 256-thread workgroup, the coupled-decay Adam update, the fp32-row argument check and the slices-per-thread ladder.
-// hgr_train.hip keeps its own reductions (they associate as (s0 + s1) + (s2 + s3): other bits) and its own AdamW.
+// reductions of a 256-thread workgroup, the coupled-decay Adam update and the fp32-row argument check; their slices-per-thread
+// ladder is hgr_by_nv4 (hgr_launch.h).  hgr_train.hip keeps its own reductions (they associate as (s0 + s1) + (s2 + s3): other bits)
+// and its own AdamW.
 #pragma once
-#include "hgr_common.h"
+#include "hgr_launch.h"
 
 // murmur3's 32-bit finaliser: the mix of hgr_dropout_counter and of the counter normal (host twin: baseline/_shared.py fmix32)
 __host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {
@@ -43,12 +44,3 @@ __device__ __forceinline__ void adam_l2_update(float &p, float g, float &m, floa
 // fp32 rows read and written as float4: 16-byte aligned, the leading dimension a multiple of 4 and at least C.  A null pointer
 // passes: an entry point that needs the operand asks for it by name first.
 static inline bool rows_f32_ok(const void *p, int64_t ld, int C) { return hgr_aligned(p, 16) && ld % 4 == 0 && ld >= C; }
-
-// A row of C <= 4096 fp32 columns over 256 threads is nv = ceil(C / 1024) float4 slices per thread: LAUNCH(NV) with NV = nv.
-#define HGR_NV_LADDER(nv, LAUNCH)     \
-    do {                              \
-        if ((nv) == 1) LAUNCH(1);     \
-        else if ((nv) == 2) LAUNCH(2); \
-        else if ((nv) == 3) LAUNCH(3); \
-        else LAUNCH(4);               \
-    } while (0)

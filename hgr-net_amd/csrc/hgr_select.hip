@@ -4,7 +4,7 @@
 // Five kernels: topk_rows and level_argmax (unfused, kept as independent checks), eval_rows (register accumulators, 17 - 32 levels),
 // eval_rows_lds (<= 16 levels) and logits_eval_rows (row stage of hgr_logits_eval).  The order, the filler rule, the threshold, the
 // ranking and the fallback rounds exist once, in the helpers below; the 64-bit key of the order is in hgr_common.h.
-#include "hgr_common.h"
+#include "hgr_launch.h"
 #include <math.h>
 
 namespace {
@@ -702,10 +702,9 @@ int hgr_logits_eval_rows_launch(const void *feat, const void *zslp, int D, int S
                                 int32_t *out_topk, int rows, int dtype, void *stream) {
     static int dbg = -1;                              // HGR_LE_DBG = 1..4: leave the row stage after level / threshold / candidate list / scan (timing experiments only)
     if (dbg < 0) dbg = hgr_lab_env("HGR_LE_DBG");   // lab builds only
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((logits_eval_rows<HGR_BF16>), dim3(rows), dim3(LE_NT), 0, (hipStream_t)stream, feat, zslp, D, S, keys, tmax, gp1, gm2, level_first,
-                                              n_levels, filler_pos, train_cols, n_train, epos, test_cols, n_test, k, out_level, out_top1, out_topk, dbg, rows);
-    else hipLaunchKernelGGL((logits_eval_rows<HGR_F16>), dim3(rows), dim3(LE_NT), 0, (hipStream_t)stream, feat, zslp, D, S, keys, tmax, gp1, gm2, level_first,
-                            n_levels, filler_pos, train_cols, n_train, epos, test_cols, n_test, k, out_level, out_top1, out_topk, dbg, rows);
+    hgr_by_dtype(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((logits_eval_rows<dt.value>), dim3(rows), dim3(LE_NT), 0, (hipStream_t)stream, feat, zslp, D, S, keys, tmax, gp1, gm2, level_first,
+                           n_levels, filler_pos, train_cols, n_train, epos, test_cols, n_test, k, out_level, out_top1, out_topk, dbg, rows); });
     HGR_CHECK_LAUNCH("hgr_logits_eval (row stage)");
     return HGR_OK;
 }

@@ -2,13 +2,11 @@
 // main.py:86-94 clip_grad_norm_ + AdamW).  The heavy products reuse hgr_gemm_nt (dX = dY . W with the weight
 // pre-transposed, dW = dY^T . X on transposed activations with the fp32 accumulate epilogue); everything here
 // is the glue around them: streaming element-wise / row-wise kernels (HBM-bound) and small fp32 products.
-#include "hgr_common.h"
+#include "hgr_launch.h"
 #include <atomic>
 #include <stdlib.h>
 
 namespace {
-
-unsigned grid1(int64_t total, int per = 256, int cap = 16384) { int64_t g = (total + per - 1) / per; return (unsigned)(g < cap ? (g > 0 ? g : 1) : cap); }
 
 // ---- y[c][r] = x[r][c], 16-bit, 64 x 64 tiles through LDS ------------------------------------------------
 __global__ __launch_bounds__(256) void transpose16_scalar(const unsigned short *__restrict__ x, int64_t ldx, unsigned short *__restrict__ y, int64_t ldy, int rows, int cols) {
@@ -383,16 +381,6 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce3(const float *__restrict__ 
         *(f32x4 *)(dst + c) = o;
     }
 }
-
-// ---- attention backward for ANY length (L <= 288 here): tiled, on the exact-fp32 MFMA ---------------------------
-// v_mfma_f32_32x32x2_f32 with operands read from fp32 LDS tiles [64][65]: lane l supplies A(i = l & 31, k = l >> 5)
-// and B(k = l >> 5, j = l & 31) per 2-deep step, so a transposed operand is just a different index function and the
-// five products (S = QK^T, dP = dO V^T, dV = P^T dO, dQ = dS K, dK = dS^T Q) need no transposed copies.  One
-// workgroup (4 waves, each a 32 x 32 quadrant of every 64 x 64 block product) per (batch, head):
-//   sweep 0: row max / sum of exp over all key blocks (online merge) and D = rowsum(dO * O);
-//   sweep 1: per query block, dQ += dS K over the key blocks;   sweep 2: per key block, dK, dV over the query blocks.
-// P is recomputed from the row statistics (flash-attention style), nothing of size L x L is ever stored.
-struct Tile { float (*t)[65]; };
 
 // C/D layout of the 32x32 MFMA shapes: accumulator register g of lane (r32, h) holds row HGR_ACC_ROW(g, h), column r32
 #define HGR_ACC_ROW(reg, h) (((reg) & 3) + 8 * ((reg) >> 2) + 4 * (h))
@@ -1168,18 +1156,17 @@ extern "C" int hgr_colsum(const void *x, int64_t ldx, int rows, int cols, int x_
     hipStream_t s = (hipStream_t)stream;
     if (x_f32 && rows <= 32 && cols % 4 == 0 && ldx % 4 == 0 && hgr_aligned(x, 16) && hgr_aligned(out, 16)) {
         const int64_t c4 = cols / 4;
-        hipLaunchKernelGGL(colsum_rows_f32, dim3(grid1(c4)), dim3(256), 0, s, (const float *)x, ldx, rows, c4, out, accumulate, alpha);
+        hipLaunchKernelGGL(colsum_rows_f32, dim3(hgr_grid1(c4, 16384)), dim3(256), 0, s, (const float *)x, ldx, rows, c4, out, accumulate, alpha);
         HGR_CHECK_LAUNCH("hgr_colsum");
         return HGR_OK;
     }
     const bool vec = cols % 64 == 0 && hgr_aligned(x, 16) && ldx % (x_f32 ? 4 : 8) == 0 && rows >= 32;
+    // fp32 input has one instantiation, under HGR_BF16, whatever dtype says
     if (vec) {
         if (x_f32) hipLaunchKernelGGL((colsum_partial_vec<HGR_BF16, true>), g, dim3(256), 0, s, x, ldx, rows, cols, scratch);
-        else if (dtype == HGR_BF16) hipLaunchKernelGGL((colsum_partial_vec<HGR_BF16, false>), g, dim3(256), 0, s, x, ldx, rows, cols, scratch);
-        else hipLaunchKernelGGL((colsum_partial_vec<HGR_F16, false>), g, dim3(256), 0, s, x, ldx, rows, cols, scratch);
+        else hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((colsum_partial_vec<dt.value, false>), g, dim3(256), 0, s, x, ldx, rows, cols, scratch); });
     } else if (x_f32) hipLaunchKernelGGL((colsum_partial<HGR_BF16, true>), g, dim3(256), 0, s, x, ldx, rows, cols, scratch);
-    else if (dtype == HGR_BF16) hipLaunchKernelGGL((colsum_partial<HGR_BF16, false>), g, dim3(256), 0, s, x, ldx, rows, cols, scratch);
-    else hipLaunchKernelGGL((colsum_partial<HGR_F16, false>), g, dim3(256), 0, s, x, ldx, rows, cols, scratch);
+    else hgr_by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((colsum_partial<dt.value, false>), g, dim3(256), 0, s, x, ldx, rows, cols, scratch); });
     colsum_finish(scratch, nrb, cols, out, accumulate, alpha, s);
     HGR_CHECK_LAUNCH("hgr_colsum");
     return HGR_OK;
@@ -1193,8 +1180,8 @@ extern "C" int hgr_transpose16_colsum(const void *x, int64_t ldx, void *y, int64
     const int nrb = (rows + 63) / 64;
     dim3 grid((cols + 63) / 64, nrb);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == HGR_BF16) hipLaunchKernelGGL(transpose16<1>, grid, dim3(256), 0, s, (const unsigned short *)x, ldx, (unsigned short *)y, ldy, rows, cols, scratch);
-    else hipLaunchKernelGGL(transpose16<2>, grid, dim3(256), 0, s, (const unsigned short *)x, ldx, (unsigned short *)y, ldy, rows, cols, scratch);
+    hgr_by_dtype(dtype, [&](auto dt) { constexpr int CS = dt.value == HGR_BF16 ? 1 : 2;
+        hipLaunchKernelGGL(transpose16<CS>, grid, dim3(256), 0, s, (const unsigned short *)x, ldx, (unsigned short *)y, ldy, rows, cols, scratch); });
     colsum_finish(scratch, nrb, cols, out, accumulate, alpha, s);
     HGR_CHECK_LAUNCH("hgr_transpose16_colsum");
     return HGR_OK;
@@ -1203,8 +1190,8 @@ extern "C" int hgr_transpose16_colsum(const void *x, int64_t ldx, void *y, int64
 extern "C" int hgr_cast16(const float *x, void *y, int64_t n, int dtype, void *stream) {
     HGR_REQUIRE(x && y && n >= 4 && n % 4 == 0 && hgr_aligned(x, 16) && hgr_aligned(y, 8), "hgr_cast16: n %% 4 == 0 and aligned operands required");
     DT_OK("hgr_cast16");
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((cast16<HGR_BF16>), dim3(grid1(n / 4)), dim3(256), 0, (hipStream_t)stream, x, (__bf16 *)y, n / 4);
-    else hipLaunchKernelGGL((cast16<HGR_F16>), dim3(grid1(n / 4)), dim3(256), 0, (hipStream_t)stream, x, (_Float16 *)y, n / 4);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((cast16<dt.value>), dim3(hgr_grid1(n / 4, 16384)), dim3(256), 0, (hipStream_t)stream, x, (E *)y, n / 4); });
     HGR_CHECK_LAUNCH("hgr_cast16");
     return HGR_OK;
 }
@@ -1214,8 +1201,8 @@ extern "C" int hgr_cast16_transpose(const float *x, int64_t ldx, void *y, int64_
     DT_OK("hgr_cast16_transpose");
     const int vec = ldx % 4 == 0 && ldy % 8 == 0 && ldyt % 8 == 0 && hgr_aligned(x, 16) && hgr_aligned(y, 16) && hgr_aligned(yt, 16);
     const dim3 grid((cols + 63) / 64, (rows + 63) / 64);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((cast16_transpose<HGR_BF16>), grid, dim3(256), 0, (hipStream_t)stream, x, ldx, (__bf16 *)y, ldy, (__bf16 *)yt, ldyt, rows, cols, vec);
-    else hipLaunchKernelGGL((cast16_transpose<HGR_F16>), grid, dim3(256), 0, (hipStream_t)stream, x, ldx, (_Float16 *)y, ldy, (_Float16 *)yt, ldyt, rows, cols, vec);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((cast16_transpose<dt.value>), grid, dim3(256), 0, (hipStream_t)stream, x, ldx, (E *)y, ldy, (E *)yt, ldyt, rows, cols, vec); });
     HGR_CHECK_LAUNCH("hgr_cast16_transpose");
     return HGR_OK;
 }
@@ -1224,14 +1211,9 @@ extern "C" int hgr_quickgelu16(const void *a, const void *du, void *out, int64_t
     HGR_REQUIRE(a && out && (!backward || du) && n >= 8 && n % 8 == 0 && hgr_aligned(a, 16) && hgr_aligned(out, 16) && hgr_aligned(du, 16), "hgr_quickgelu16: bad arguments");
     DT_OK("hgr_quickgelu16");
     hipStream_t s = (hipStream_t)stream;
-    const dim3 g(grid1(n / 8));
-    if (dtype == HGR_BF16) {
-        if (backward) hipLaunchKernelGGL((gelu16<HGR_BF16, true>), g, dim3(256), 0, s, (const __bf16 *)a, (const __bf16 *)du, (__bf16 *)out, n / 8);
-        else hipLaunchKernelGGL((gelu16<HGR_BF16, false>), g, dim3(256), 0, s, (const __bf16 *)a, (const __bf16 *)du, (__bf16 *)out, n / 8);
-    } else {
-        if (backward) hipLaunchKernelGGL((gelu16<HGR_F16, true>), g, dim3(256), 0, s, (const _Float16 *)a, (const _Float16 *)du, (_Float16 *)out, n / 8);
-        else hipLaunchKernelGGL((gelu16<HGR_F16, false>), g, dim3(256), 0, s, (const _Float16 *)a, (const _Float16 *)du, (_Float16 *)out, n / 8);
-    }
+    const dim3 g(hgr_grid1(n / 8, 16384));
+    hgr_by_dtype(dtype, [&](auto dt) { hgr_by_flag(backward, [&](auto bwd) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((gelu16<dt.value, bwd.value>), g, dim3(256), 0, s, (const E *)a, (const E *)du, (E *)out, n / 8); }); });
     HGR_CHECK_LAUNCH("hgr_quickgelu16");
     return HGR_OK;
 }
@@ -1249,15 +1231,8 @@ static int layernorm_bwd_entry(const char *name, const void *dy, int dy_f32, con
     float *pc = dx16_colsum ? cs + ((int64_t)(nw + 511) / 512) * W : nullptr;   // third partial matrix behind it (hgr_layernorm_bwd_scratch_floats counts it)
     hipStream_t s = (hipStream_t)stream;
     const int nvl = (W / 4 + 63) / 64;
-#define HGR_LNB(NVV)                                                                                                             \
-    do {                                                                                                                         \
-        if (dy_f32 && dtype == HGR_BF16) hipLaunchKernelGGL((layernorm_bwd<HGR_BF16, true, NVV>), dim3(blocks), dim3(256), 0, s, dy, x, gamma, dx, pg, pb, rows, W, row_mul, row_idx, eps, (__bf16 *)dx16, pc); \
-        else if (dy_f32) hipLaunchKernelGGL((layernorm_bwd<HGR_F16, true, NVV>), dim3(blocks), dim3(256), 0, s, dy, x, gamma, dx, pg, pb, rows, W, row_mul, row_idx, eps, (_Float16 *)dx16, pc); \
-        else if (dtype == HGR_BF16) hipLaunchKernelGGL((layernorm_bwd<HGR_BF16, false, NVV>), dim3(blocks), dim3(256), 0, s, dy, x, gamma, dx, pg, pb, rows, W, row_mul, row_idx, eps, (__bf16 *)dx16, pc); \
-        else hipLaunchKernelGGL((layernorm_bwd<HGR_F16, false, NVV>), dim3(blocks), dim3(256), 0, s, dy, x, gamma, dx, pg, pb, rows, W, row_mul, row_idx, eps, (_Float16 *)dx16, pc); \
-    } while (0)
-    if (nvl <= 1) HGR_LNB(1); else if (nvl <= 2) HGR_LNB(2); else if (nvl <= 4) HGR_LNB(4); else if (nvl <= 8) HGR_LNB(8); else HGR_LNB(16);
-#undef HGR_LNB
+    hgr_by_nv_pow2(nvl, [&](auto nv) { hgr_by_flag(dy_f32, [&](auto f32) { hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((layernorm_bwd<dt.value, f32.value, nv.value>), dim3(blocks), dim3(256), 0, s, dy, x, gamma, dx, pg, pb, rows, W, row_mul, row_idx, eps, (E *)dx16, pc); }); }); });
     HGR_CHECK_LAUNCH(name);
     if (hgr_aligned(dgamma, 16) && hgr_aligned(dbeta, 16) && hgr_aligned(dx16_colsum, 16)) {      // (W % 4 == 0 is required above)
         hipLaunchKernelGGL(ln_bwd_reduce3, dim3((W + 63) / 64, pc ? 3 : 2), dim3(256), 0, s, pg, pb, pc, nw, W, dgamma, dbeta, dx16_colsum);
@@ -1307,25 +1282,12 @@ static int mha_bwd_entry(const char *name, const void *qkv, const void *out, con
     HGR_REQUIRE(dtype == HGR_BF16 || dtype == HGR_F16, "%s: bad dtype %d", name, dtype);
     hipStream_t s = (hipStream_t)stream;
     const dim3 g(B * heads);
-    if (L <= 32) {           // one 32 x 32 block per (batch, head): the statistics are recomputed in registers, `stats` is not needed
-        if (dtype == HGR_BF16) {
-            if (causal) hipLaunchKernelGGL((mha_bwd_wave<HGR_BF16, true>), g, dim3(64), 0, s, (const __bf16 *)qkv, (const __bf16 *)dout, (__bf16 *)dqkv, L, heads, colpart);
-            else hipLaunchKernelGGL((mha_bwd_wave<HGR_BF16, false>), g, dim3(64), 0, s, (const __bf16 *)qkv, (const __bf16 *)dout, (__bf16 *)dqkv, L, heads, colpart);
-        } else {
-            if (causal) hipLaunchKernelGGL((mha_bwd_wave<HGR_F16, true>), g, dim3(64), 0, s, (const _Float16 *)qkv, (const _Float16 *)dout, (_Float16 *)dqkv, L, heads, colpart);
-            else hipLaunchKernelGGL((mha_bwd_wave<HGR_F16, false>), g, dim3(64), 0, s, (const _Float16 *)qkv, (const _Float16 *)dout, (_Float16 *)dqkv, L, heads, colpart);
-        }
-    }
-    else {
-        const float2 *st = (const float2 *)stats;
-#define HGR_MT(CAUS)                                                                                                              \
-    do {                                                                                                                          \
-        if (dtype == HGR_BF16) hipLaunchKernelGGL((mha_bwd_tiled<HGR_BF16, CAUS>), g, dim3(256), 0, s, (const __bf16 *)qkv, (const __bf16 *)out, (const __bf16 *)dout, (__bf16 *)dqkv, L, heads, st, colpart); \
-        else hipLaunchKernelGGL((mha_bwd_tiled<HGR_F16, CAUS>), g, dim3(256), 0, s, (const _Float16 *)qkv, (const _Float16 *)out, (const _Float16 *)dout, (_Float16 *)dqkv, L, heads, st, colpart); \
-    } while (0)
-        if (causal) HGR_MT(true); else HGR_MT(false);
-#undef HGR_MT
-    }
+    if (L <= 32)             // one 32 x 32 block per (batch, head): the statistics are recomputed in registers, `stats` is not needed
+        hgr_by_dtype(dtype, [&](auto dt) { hgr_by_flag(causal, [&](auto caus) { typedef typename decltype(dt)::elem E;
+            hipLaunchKernelGGL((mha_bwd_wave<dt.value, caus.value>), g, dim3(64), 0, s, (const E *)qkv, (const E *)dout, (E *)dqkv, L, heads, colpart); }); });
+    else
+        hgr_by_flag(causal, [&](auto caus) { hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+            hipLaunchKernelGGL((mha_bwd_tiled<dt.value, caus.value>), g, dim3(256), 0, s, (const E *)qkv, (const E *)out, (const E *)dout, (E *)dqkv, L, heads, (const float2 *)stats, colpart); }); });
     HGR_CHECK_LAUNCH(name);
     return HGR_OK;
 }
@@ -1375,7 +1337,7 @@ extern "C" int hgr_matmul_f32(const float *A, int64_t sam, int64_t sak, const fl
 
 extern "C" int hgr_embed_scatter_add(const int64_t *tokens, int64_t ld_tokens, const float *dx, float *dtable, int n, int L, int W, int vocab, void *stream) {
     HGR_REQUIRE(tokens && dx && dtable && n >= 1 && L >= 1 && W >= 1 && vocab >= 1 && ld_tokens >= L, "hgr_embed_scatter_add: bad arguments");
-    hipLaunchKernelGGL(embed_scatter_add, dim3(grid1((int64_t)n * L * W)), dim3(256), 0, (hipStream_t)stream, tokens, ld_tokens, dx, dtable, n, L, W, vocab);
+    hipLaunchKernelGGL(embed_scatter_add, dim3(hgr_grid1((int64_t)n * L * W, 16384)), dim3(256), 0, (hipStream_t)stream, tokens, ld_tokens, dx, dtable, n, L, W, vocab);
     HGR_CHECK_LAUNCH("hgr_embed_scatter_add");
     return HGR_OK;
 }
@@ -1410,7 +1372,7 @@ extern "C" int hgr_sumsq(const float *x, int64_t n, float *out, void *stream) {
     HGR_REQUIRE(x && out && n >= 1, "hgr_sumsq: bad arguments");
     static std::atomic<unsigned> next_slot{0};                  // consecutive launches take consecutive scratch slots (see the kernel)
     const int slot = (int)(next_slot.fetch_add(1u, std::memory_order_relaxed) % SUMSQ_SLOTS);
-    hipLaunchKernelGGL(sumsq, dim3(grid1(n, 256, 1024)), dim3(256), 0, (hipStream_t)stream, x, n, out, slot);
+    hipLaunchKernelGGL(sumsq, dim3(hgr_grid1(n, 1024)), dim3(256), 0, (hipStream_t)stream, x, n, out, slot);
     HGR_CHECK_LAUNCH("hgr_sumsq");
     return HGR_OK;
 }
@@ -1419,28 +1381,28 @@ extern "C" int hgr_adamw(float *p, const float *g, float *m, float *v, int64_t n
                          int step, const float *sumsq_total, float max_norm, float grad_scale, void *stream) {
     HGR_REQUIRE(p && g && m && v && n >= 1 && step >= 1, "hgr_adamw: bad arguments");
     const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw, dim3(grid1(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, wd, bc1, bc2, sumsq_total, max_norm, grad_scale);
+    hipLaunchKernelGGL(adamw, dim3(hgr_grid1(n, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, wd, bc1, bc2, sumsq_total, max_norm, grad_scale);
     HGR_CHECK_LAUNCH("hgr_adamw");
     return HGR_OK;
 }
 
 extern "C" int hgr_rows_axpy(float *dst, int64_t dst_mul, const int32_t *dst_idx, const float *src, int rows, int W, float alpha, void *stream) {
     HGR_REQUIRE(dst && src && rows >= 1 && W >= 1 && dst_mul >= 0 && (dst_mul >= 1 || dst_idx), "hgr_rows_axpy: bad arguments");
-    hipLaunchKernelGGL(rows_axpy, dim3(grid1((int64_t)rows * W)), dim3(256), 0, (hipStream_t)stream, dst, dst_mul, dst_idx, src, rows, W, alpha);
+    hipLaunchKernelGGL(rows_axpy, dim3(hgr_grid1((int64_t)rows * W, 16384)), dim3(256), 0, (hipStream_t)stream, dst, dst_mul, dst_idx, src, rows, W, alpha);
     HGR_CHECK_LAUNCH("hgr_rows_axpy");
     return HGR_OK;
 }
 
 extern "C" int hgr_rows_gather(float *dst, const float *src, const int32_t *idx, int rows, int W, void *stream) {
     HGR_REQUIRE(dst && src && idx && rows >= 1 && W >= 1, "hgr_rows_gather: bad arguments");
-    hipLaunchKernelGGL(rows_gather, dim3(grid1((int64_t)rows * W)), dim3(256), 0, (hipStream_t)stream, dst, src, idx, rows, W);
+    hipLaunchKernelGGL(rows_gather, dim3(hgr_grid1((int64_t)rows * W, 16384)), dim3(256), 0, (hipStream_t)stream, dst, src, idx, rows, W);
     HGR_CHECK_LAUNCH("hgr_rows_gather");
     return HGR_OK;
 }
 
 extern "C" int hgr_ctx_splice(float *x, const float *ctx, const float *positional_embedding, int n, int L, int W, int n_ctx, void *stream) {
     HGR_REQUIRE(x && ctx && positional_embedding && n >= 1 && n_ctx >= 1 && L >= n_ctx + 2 && W >= 1, "hgr_ctx_splice: bad arguments (L >= n_ctx + 2)");
-    hipLaunchKernelGGL(ctx_splice, dim3(grid1((int64_t)n * n_ctx * W)), dim3(256), 0, (hipStream_t)stream, x, ctx, positional_embedding, n, L, W, n_ctx);
+    hipLaunchKernelGGL(ctx_splice, dim3(hgr_grid1((int64_t)n * n_ctx * W, 16384)), dim3(256), 0, (hipStream_t)stream, x, ctx, positional_embedding, n, L, W, n_ctx);
     HGR_CHECK_LAUNCH("hgr_ctx_splice");
     return HGR_OK;
 }

@@ -7,11 +7,9 @@
 // BatchNorm runs with running statistics even in training (clip_tree.py:46 keeps the model in eval()), so the forward
 // uses conv weights with BN folded in (w' = w * gamma / sigma, b' = beta - mean * gamma / sigma: hgr_bn_fold) and the
 // backward produces gradients of w' and b', which hgr_bn_unfold_grad maps back to conv.weight, bn.weight and bn.bias.
-#include "hgr_common.h"
+#include "hgr_launch.h"
 
 namespace {
-
-unsigned grid_for(int64_t total) { return (unsigned)((total + 255) / 256 < 32768 ? (total + 255) / 256 : 32768); }
 
 // dy *= (y > 0)   (ReLU backward from the saved OUTPUT), in place or to `out`
 template <int DT>
@@ -167,8 +165,8 @@ __global__ __launch_bounds__(256) void bn_unfold_grad(const float *__restrict__ 
 extern "C" int hgr_relu_bwd16(const void *dy, const void *y, void *out, int64_t n, int dtype, void *stream) {
     HGR_REQUIRE(dy && y && out && n >= 8 && n % 8 == 0, "hgr_relu_bwd16: n=%lld must be a positive multiple of 8", (long long)n);
     HGR_REQUIRE(hgr_aligned(dy, 16) && hgr_aligned(y, 16) && hgr_aligned(out, 16) && (dtype == HGR_BF16 || dtype == HGR_F16), "hgr_relu_bwd16: bad operand");
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((relu_bwd16<HGR_BF16>), dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)dy, (const __bf16 *)y, (__bf16 *)out, n / 8);
-    else hipLaunchKernelGGL((relu_bwd16<HGR_F16>), dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)dy, (const _Float16 *)y, (_Float16 *)out, n / 8);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((relu_bwd16<dt.value>), dim3(hgr_grid1(n / 8, 32768)), dim3(256), 0, (hipStream_t)stream, (const E *)dy, (const E *)y, (E *)out, n / 8); });
     HGR_CHECK_LAUNCH("hgr_relu_bwd16");
     return HGR_OK;
 }
@@ -176,8 +174,8 @@ extern "C" int hgr_relu_bwd16(const void *dy, const void *y, void *out, int64_t 
 extern "C" int hgr_add16(const void *a, const void *b, void *out, int64_t n, int dtype, void *stream) {
     HGR_REQUIRE(a && b && out && n >= 8 && n % 8 == 0, "hgr_add16: n=%lld must be a positive multiple of 8", (long long)n);
     HGR_REQUIRE(hgr_aligned(a, 16) && hgr_aligned(b, 16) && hgr_aligned(out, 16) && (dtype == HGR_BF16 || dtype == HGR_F16), "hgr_add16: bad operand");
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((add16<HGR_BF16>), dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)a, (const __bf16 *)b, (__bf16 *)out, n / 8);
-    else hipLaunchKernelGGL((add16<HGR_F16>), dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)a, (const _Float16 *)b, (_Float16 *)out, n / 8);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((add16<dt.value>), dim3(hgr_grid1(n / 8, 32768)), dim3(256), 0, (hipStream_t)stream, (const E *)a, (const E *)b, (E *)out, n / 8); });
     HGR_CHECK_LAUNCH("hgr_add16");
     return HGR_OK;
 }
@@ -186,8 +184,8 @@ extern "C" int hgr_avgpool2_bwd_nhwc(const void *dy, void *dx, int B, int H, int
     HGR_REQUIRE(dy && dx && B >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && C >= 8 && C % 8 == 0, "hgr_avgpool2_bwd_nhwc: bad geometry B=%d H=%d W=%d C=%d", B, H, W, C);
     HGR_REQUIRE(hgr_aligned(dy, 16) && hgr_aligned(dx, 16) && (dtype == HGR_BF16 || dtype == HGR_F16), "hgr_avgpool2_bwd_nhwc: bad operand");
     const int64_t total = (int64_t)B * H * W * (C / 8);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((avgpool2_bwd<HGR_BF16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)dy, (__bf16 *)dx, B, H, W, C);
-    else hipLaunchKernelGGL((avgpool2_bwd<HGR_F16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)dy, (_Float16 *)dx, B, H, W, C);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((avgpool2_bwd<dt.value>), dim3(hgr_grid1(total, 32768)), dim3(256), 0, (hipStream_t)stream, (const E *)dy, (E *)dx, B, H, W, C); });
     HGR_CHECK_LAUNCH("hgr_avgpool2_bwd_nhwc");
     return HGR_OK;
 }
@@ -196,8 +194,8 @@ extern "C" int hgr_attnpool_tokens_bwd(const void *dtok, void *dx, int B, int S,
     HGR_REQUIRE(dtok && dx && B >= 1 && S >= 1 && C >= 8 && C % 8 == 0, "hgr_attnpool_tokens_bwd: bad arguments");
     HGR_REQUIRE(hgr_aligned(dtok, 16) && hgr_aligned(dx, 16) && (dtype == HGR_BF16 || dtype == HGR_F16), "hgr_attnpool_tokens_bwd: bad operand");
     const int64_t total = (int64_t)B * S * (C / 8);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((attnpool_tokens_bwd<HGR_BF16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)dtok, (__bf16 *)dx, B, S, C);
-    else hipLaunchKernelGGL((attnpool_tokens_bwd<HGR_F16>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)dtok, (_Float16 *)dx, B, S, C);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((attnpool_tokens_bwd<dt.value>), dim3(hgr_grid1(total, 32768)), dim3(256), 0, (hipStream_t)stream, (const E *)dtok, (E *)dx, B, S, C); });
     HGR_CHECK_LAUNCH("hgr_attnpool_tokens_bwd");
     return HGR_OK;
 }
@@ -207,8 +205,8 @@ extern "C" int hgr_im2col3x3_t(const void *xt, void *out, int B, int H, int W, i
     const int64_t M = (int64_t)B * H * W;
     HGR_REQUIRE(ld >= M && ld % 8 == 0 && hgr_aligned(out, 16) && (dtype == HGR_BF16 || dtype == HGR_F16), "hgr_im2col3x3_t: ld=%lld must be >= B*H*W and a multiple of 8, out 16-byte aligned", (long long)ld);
     const dim3 grid((unsigned)((ld + 2047) / 2048 < 4096 ? (ld + 2047) / 2048 : 4096), (unsigned)(9 * C));
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((im2col3x3_t<HGR_BF16>), grid, dim3(256), 0, (hipStream_t)stream, (const __bf16 *)xt, (__bf16 *)out, H, W, C, M, ld);
-    else hipLaunchKernelGGL((im2col3x3_t<HGR_F16>), grid, dim3(256), 0, (hipStream_t)stream, (const _Float16 *)xt, (_Float16 *)out, H, W, C, M, ld);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((im2col3x3_t<dt.value>), grid, dim3(256), 0, (hipStream_t)stream, (const E *)xt, (E *)out, H, W, C, M, ld); });
     HGR_CHECK_LAUNCH("hgr_im2col3x3_t");
     return HGR_OK;
 }
@@ -217,8 +215,8 @@ extern "C" int hgr_bn_fold(const float *w, const float *gamma, const float *beta
                            void *w16, float *bias, int Cout, int Cin, int khw, int Kp, int dtype, void *stream) {
     HGR_REQUIRE(w && gamma && beta && mean && var && w16 && bias, "hgr_bn_fold: null operand");
     HGR_REQUIRE(Cout >= 1 && Cin >= 1 && (khw == 1 || khw == 9) && Kp >= Cin * khw && (dtype == HGR_BF16 || dtype == HGR_F16), "hgr_bn_fold: bad shape Cout=%d Cin=%d khw=%d Kp=%d", Cout, Cin, khw, Kp);
-    if (dtype == HGR_BF16) hipLaunchKernelGGL((bn_fold<HGR_BF16>), dim3(Cout), dim3(256), 0, (hipStream_t)stream, w, gamma, beta, mean, var, eps, (__bf16 *)w16, bias, Cin, khw, Kp);
-    else hipLaunchKernelGGL((bn_fold<HGR_F16>), dim3(Cout), dim3(256), 0, (hipStream_t)stream, w, gamma, beta, mean, var, eps, (_Float16 *)w16, bias, Cin, khw, Kp);
+    hgr_by_dtype(dtype, [&](auto dt) { typedef typename decltype(dt)::elem E;
+        hipLaunchKernelGGL((bn_fold<dt.value>), dim3(Cout), dim3(256), 0, (hipStream_t)stream, w, gamma, beta, mean, var, eps, (E *)w16, bias, Cin, khw, Kp); });
     HGR_CHECK_LAUNCH("hgr_bn_fold");
     return HGR_OK;
 }

@@ -64,7 +64,7 @@ def tag(dt):
 
 # ==== dispatch restatements ========================================================================================================
 def grid1(total, per=256, cap=16384):
-    """csrc/hgr_train.hip grid1: blocks of `per` threads, at most `cap` of them."""
+    """csrc/hgr_launch.h hgr_grid1(total, cap, per): blocks of `per` threads, at most `cap` of them."""
     g = (total + per - 1) // per
     return min(max(g, 1), cap)
 
