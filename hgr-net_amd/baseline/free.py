@@ -31,7 +31,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .. import ops
+from .. import ops, wgrad
 from ._shared import K_SLICE, TOP, BufferPool, TreeScorer, fmix32, mean_rows, need_device, sliced_matmul_f32  # noqa: F401
 from .cnzsl import synth_rows  # noqa: F401
 from .dgp_eval import ListTree
@@ -455,9 +455,7 @@ class FREEClassifier(TreeScorer):
             d32 = self._buf("d32", (b, npad), zero=True)   # ce_rows writes n columns: the padding columns stay zero
             ops.ce_rows(logits[:, :n], lab, loss_rows, d32, gscale=1.0)
             ops.cast16(d32, d16)
-        s0 = ops.tn_slices(npad, k, b)
-        kc = -(-(-(-b // s0)) // 64) * 64
-        s = -(-b // kc)
+        _, s, kc, _ = wgrad.plan(npad, k, b)
         part = self._buf("part", (s, npad, k))
         ops.gemm_tn_splitk(d16, big, part, kc)
         gb = self._buf("gb", (npad,))

@@ -26,22 +26,17 @@ from typing import Callable, List, Optional
 import torch
 
 from . import ops
-from ._lib import EPI_ACCUM, EPI_BIAS, EPI_BIAS_RESIDUAL, EPI_NONE, EPI_QGELU_GRAD16, HgrError
+from ._lib import EPI_BIAS, EPI_BIAS_RESIDUAL, EPI_QGELU_GRAD16, HgrError
 from .clip.model import VisionTransformer
+from .wgrad import WeightGrad, grad as _grad, pad64 as _pad64
 
 
 import os
 
-# weight gradients from untransposed operands (hgr_gemm_tn_splitk); HGR_WGRAD=nt keeps the transposing route for A/B runs
-WGRAD_TN = os.environ.get("HGR_WGRAD", "tn") != "nt"
 # QuickGELU backward in the epilogue of the c_proj data-gradient GEMM; HGR_GELU_BWD_FUSED=0 keeps the separate pass for A/B runs
 GELU_BWD_FUSED = os.environ.get("HGR_GELU_BWD_FUSED", "1") != "0"
 GELU_FWD_FUSED = os.environ.get("HGR_GELU_FWD_FUSED", "1") != "0"     # c_fc forward writes pre-activation and activation in one launch
 COLSUM_FUSED = os.environ.get("HGR_COLSUM_FUSED", "1") != "0"         # bias gradients as by-products of the kernels that produce dY (no hgr_colsum pass over dY)
-
-
-def _pad64(n: int) -> int:
-    return (n + 63) // 64 * 64
 
 
 def check_distinct_ids(id_lists) -> None:
@@ -54,12 +49,6 @@ def check_distinct_ids(id_lists) -> None:
             if i in seen:
                 raise ValueError(f"OMTrainer: inner step {j} lists node {i} twice (ids must be distinct: a duplicate row would receive two gradients)")
             seen.add(i)
-
-
-def _grad(p: torch.nn.Parameter) -> torch.Tensor:
-    if p.grad is None:
-        p.grad = torch.zeros_like(p.data, dtype=torch.float32)
-    return p.grad
 
 
 class _Lin:
@@ -108,7 +97,7 @@ class Engine:
         self.dt = ops.TORCH16[ops.dtype_code(dtype)]
         self.dev = next(clip_model.parameters()).device
         self._scratch = None
-        self._part = None
+        self.wgrad = WeightGrad(self.dt, self.dev, self.scratch)      # one set of weight-gradient buffers for every layer of both towers
 
     # -- helpers -------------------------------------------------------------------------------
     def scratch(self, n: int) -> torch.Tensor:
@@ -140,71 +129,18 @@ class Engine:
         self.rn = None
         if not vit:
             from .training_rn import RNTower                # ModifiedResNet (the reference's README trains --arch RN50)
-            self.rn = RNTower(m.visual, dt, self.scratch)
+            self.rn = RNTower(m.visual, dt, self.scratch, self.wgrad)
 
     def _linear_bwd(self, lin: _Lin, dy16: torch.Tensor, x16: torch.Tensor, m: int, need_dx: bool = True,
                     gelu_pre: Optional[torch.Tensor] = None, dy_colsum: Optional[torch.Tensor] = None,
                     dx_colsum: Optional[list] = None, bias_done: bool = False) -> Optional[torch.Tensor]:
-        """dW += dY^T X, db += colsum(dY); returns dX = dY W (16-bit) if wanted.  dy16 [m, n], x16 [m, k].
-        ``dy_colsum``: per-64-row column sums of dy16 its producer already made ([ceil(m / 64), n] fp32): db comes from them,
-        dy16 is not read a third time.  ``dx_colsum`` (a list, with ``gelu_pre``): receives such sums of the returned dX.
+        """dW += dY^T X, db += colsum(dY) (wgrad.py); returns dX = dY W (16-bit) if wanted.  dy16 [m, n], x16 [m, >= k].
+        ``dy_colsum``: partial column sums of dy16 its producer already made (fp32 [rows, n]): db comes from them, dy16 is not
+        read a third time.  ``dx_colsum`` (a list, with ``gelu_pre``): receives such sums of the returned dX.
         ``bias_done``: the producer of dy16 already added its column sums to the bias gradient (hgr_layernorm_bwd_cast_colsum)."""
-        dev, dt = self.dev, self.dt
-        xq = x16[:, : lin.k] if x16.shape[1] != lin.k else x16
-        if WGRAD_TN and lin.n % 8 == 0 and lin.k % 8 == 0 and dy16.stride(0) % 8 == 0 and xq.stride(0) % 8 == 0 \
-                and dy16.data_ptr() % 16 == 0 and xq.data_ptr() % 16 == 0:
-            # operands as they lie in memory (hgr_gemm_tn_splitk): no transposed copies of dY and X
-            gw = _grad(lin.weight).view(lin.n, lin.k)
-            s = ops.tn_slices(lin.n, lin.k, m)
-            kc = _pad64(-(-m // s))
-            s = -(-m // kc)
-            need = s * lin.n * lin.k
-            if self._part is None or self._part.numel() < need:
-                self._part = torch.empty(need, dtype=torch.float32, device=dev)
-            part = self._part[:need].view(s, lin.n * lin.k)
-            ops.gemm_tn_splitk(dy16, xq, part, kc)
-            if s > 1:
-                ops.colsum(part, gw.view(-1), self.scratch(lin.n * lin.k), accumulate=True)
-            else:
-                gw.view(-1).add_(part[0])
-            if lin.bias is not None and not bias_done:
-                if dy_colsum is not None:
-                    ops.colsum(dy_colsum, _grad(lin.bias), self.scratch(((dy_colsum.shape[0] + 511) // 512) * lin.n), accumulate=True)
-                else:
-                    ops.colsum(dy16, _grad(lin.bias), self.scratch(((m + 511) // 512) * lin.n), accumulate=True)
-            return self._linear_dx(lin, dy16, m, gelu_pre, dx_colsum) if need_dx else None
-        mp = _pad64(m)
-        alloc = torch.empty if mp == m else torch.zeros           # the pad columns must be zero, the rest is overwritten
-        dyt = alloc(lin.n, mp, dtype=dt, device=dev)
-        xt = alloc(lin.k, mp, dtype=dt, device=dev)
-        fused_bias = lin.bias is not None and not bias_done and dy16.stride(0) % 8 == 0 and dy16.data_ptr() % 16 == 0
-        if fused_bias:      # db rides on the transposition of dY
-            ops.transpose16_colsum(dy16, dyt, _grad(lin.bias), self.scratch(((m + 63) // 64) * lin.n), accumulate=True)
-        else:
-            ops.transpose16(dy16, dyt)
-        ops.transpose16(x16[:, : lin.k] if x16.shape[1] != lin.k else x16, xt)
-        gw = _grad(lin.weight).view(lin.n, lin.k)
-        if lin.n >= 256 and lin.k >= 256:                     # 256^2 tiles, one workgroup per CU
-            tiles = -(-lin.n // 256) * -(-lin.k // 256)
-            s = min(mp // 128, -(-256 // tiles))
-        else:
-            tiles = -(-lin.n // 128) * -(-lin.k // 128)
-            s = min(mp // 64, -(-512 // tiles))
-        if s > 1:
-            # few output tiles, long reduction: slice K over the chip, add the fp32 partials in a fixed order
-            kc = _pad64(-(-mp // s))
-            s = -(-mp // kc)
-            need = s * lin.n * lin.k
-            if self._part is None or self._part.numel() < need:
-                self._part = torch.empty(need, dtype=torch.float32, device=dev)
-            part = self._part[:need].view(s, lin.n * lin.k)
-            ops.gemm_nt_splitk(dyt, xt, part, kc)
-            ops.colsum(part, gw.view(-1), self.scratch(lin.n * lin.k), accumulate=True)
-        else:
-            ops.gemm_nt(dyt, xt, gw, epilogue=EPI_ACCUM)
-        if lin.bias is not None and not fused_bias and not bias_done:
-            ops.colsum(dy16, _grad(lin.bias), self.scratch(((m + 511) // 512) * lin.n), accumulate=True)
-        return self._linear_dx(lin, dy16, m, gelu_pre) if need_dx else None
+        self.wgrad.add(_grad(lin.weight).view(lin.n, lin.k), dy16, x16[:, : lin.k],
+                       gb=_grad(lin.bias) if lin.bias is not None and not bias_done else None, dy_colsum=dy_colsum)
+        return self._linear_dx(lin, dy16, m, gelu_pre, dx_colsum) if need_dx else None
 
     def _linear_dx(self, lin: _Lin, dy16: torch.Tensor, m: int, gelu_pre: Optional[torch.Tensor] = None, dx_colsum: Optional[list] = None) -> torch.Tensor:
         """dX = dY W (16-bit).  With ``gelu_pre`` (the QuickGELU pre-activation that produced this layer's input) the GEMM's

@@ -7,9 +7,9 @@ model/clip_tree.py:46), 1x1 convolutions = `hgr_gemm_nt`, 3x3 = the implicit-GEM
 
   * dX: 1x1 -> NT product against the transposed weight; 3x3 -> `hgr_conv3x3_nhwc_plain` with the flipped, in/out
     swapped weight (all 3x3 convolutions that need a data gradient have stride 1);
-  * dW' = dY^T . Xcol is a product with a tiny output and a reduction over every pixel of the batch: both operands are
-    transposed (3x3: `hgr_im2col3x3_t` builds Xcol^T from X^T, nine shifted masked copies), `hgr_gemm_nt_splitk`
-    spreads the reduction over the chip and `hgr_colsum` adds the fp32 partials; db' = column sum of dY;
+  * dW' = dY^T . Xcol is a product with a tiny output and a reduction over every pixel of the batch: wgrad.py reads both
+    operands as stored (3x3: `hgr_conv3x3_wgrad_splitk` forms the im2col columns in its loader), spreads the reduction over
+    the chip and adds the fp32 partials with `hgr_colsum`; db' = column sum of dY;
   * `hgr_bn_unfold_grad` maps (dW', db') to conv.weight / bn.weight / bn.bias gradients once per step.
 
 The attention pool runs as a packed-QKV self-attention over all 1 + HW tokens (`hgr_mha` / `hgr_mha_bwd`; only token
@@ -23,16 +23,7 @@ import torch
 
 from . import ops
 from ._lib import EPI_BIAS, EPI_BIAS_ADD16_RELU, EPI_BIAS_RELU
-
-
-def _pad64(n: int) -> int:
-    return (n + 63) // 64 * 64
-
-
-def _grad(p: torch.nn.Parameter) -> torch.Tensor:
-    if p.grad is None:
-        p.grad = torch.zeros_like(p.data, dtype=torch.float32)
-    return p.grad
+from .wgrad import WeightGrad, grad as _grad, pad64 as _pad64
 
 
 class _ConvBN:
@@ -85,8 +76,8 @@ class _Block:
 class RNTower:
     """Training-mode ModifiedResNet: `fwd(image) -> (feat fp32 [B, D], saves)`, `bwd(dfeat, saves)` adds every parameter gradient."""
 
-    def __init__(self, visual, dt: torch.dtype, scratch):
-        self.v, self.dt, self.scratch = visual, dt, scratch
+    def __init__(self, visual, dt: torch.dtype, scratch, wgrad: WeightGrad):
+        self.v, self.dt, self.scratch, self.wgrad = visual, dt, scratch, wgrad
         self.dev = visual.conv1.weight.device
         width = visual.conv3.weight.shape[0]
         if width % 64 or (width & (width - 1)):
@@ -126,77 +117,9 @@ class RNTower:
             v.zero_()
         return v
 
-    def _wgrad(self, gw: torch.Tensor, dy16: torch.Tensor, xcol_t: torch.Tensor, m: int, gb: Optional[torch.Tensor] = None) -> None:
-        """gw [Cout, >= K] += dy16[:m]^T . xcol_t^T   (xcol_t [K, Mp], zero beyond column m);  gb [Cout] += column sums of dy16
-        from the same pass that transposes it."""
-        cout, (k, mp) = dy16.shape[1], xcol_t.shape
-        dyt = self._tmp("dyt", (cout, mp), self.dt, zero=mp != m)
-        if gb is not None and dy16.stride(0) % 8 == 0 and dy16.data_ptr() % 16 == 0:
-            ops.transpose16_colsum(dy16, dyt, gb, self.scratch(((dy16.shape[0] + 63) // 64) * cout), accumulate=True)
-        else:
-            ops.transpose16(dy16, dyt)
-            if gb is not None:
-                self._bias_grad(gb, dy16)
-        if cout >= 256 and k >= 256:                          # 256^2 tiles, one workgroup per CU
-            tiles = -(-cout // 256) * -(-k // 256)
-            s = max(1, min(mp // 128, -(-256 // tiles)))
-        else:
-            tiles = -(-cout // 128) * -(-k // 128)
-            s = max(1, min(mp // 64, -(-768 // tiles)))
-        kc = _pad64(-(-mp // s))
-        s = -(-mp // kc)
-        part = self._tmp("part", (s, cout * k), torch.float32)
-        ops.gemm_nt_splitk(dyt, xcol_t, part, kc)
-        if gw.shape[1] == k:
-            ops.colsum(part, gw.view(-1), self.scratch(cout * k), accumulate=True)
-        else:                                                # accumulator is K-padded: reduce, then add the live columns
-            red = self._tmp("red", (cout, k), torch.float32)
-            ops.colsum(part, red.view(-1), self.scratch(cout * k), accumulate=False)
-            gw[:, :k].add_(red)
-
-    def _bias_grad(self, gb: torch.Tensor, dy16: torch.Tensor) -> None:
-        m, n = dy16.shape
-        ops.colsum(dy16, gb, self.scratch(((m + 511) // 512) * n), accumulate=True)
-
-    def _reduce(self, part: torch.Tensor, s: int, gw: torch.Tensor, cout: int, k: int) -> None:
-        """gw [Cout, >= K] += sum of the s fp32 slices part [s, Cout * K]."""
-        if gw.shape[1] == k and s > 1:
-            ops.colsum(part, gw.view(-1), self.scratch(cout * k), accumulate=True)
-            return
-        if s > 1:
-            red = self._tmp("red", (cout, k), torch.float32)
-            ops.colsum(part, red.view(-1), self.scratch(cout * k), accumulate=False)
-        else:
-            red = part[0].view(cout, k)
-        gw[:, :k].add_(red)
-
-    def _wgrad_tn(self, gw: torch.Tensor, dy16: torch.Tensor, x16: torch.Tensor, gb: Optional[torch.Tensor], conv: Optional[tuple] = None) -> bool:
-        """Weight (and bias) gradient from the operands as stored: dW = dY^T X (1x1) or dY^T im2col(X) (conv = (b, h, c))."""
-        from .training import WGRAD_TN
-        m, cout = dy16.shape
-        k = 9 * conv[2] if conv else x16.shape[1]
-        if not WGRAD_TN or cout % 8 or k % 8 or dy16.stride(0) % 8 or dy16.data_ptr() % 16 or x16.data_ptr() % 16 or not x16.is_contiguous():
-            return False
-        s = ops.splitk_slices(-(-cout // 128) * -(-k // 128), m) if conv else ops.tn_slices(cout, k, m)
-        kc = _pad64(-(-m // s))
-        s = -(-m // kc)
-        part = self._tmp("part", (s, cout * k), torch.float32)
-        if conv:
-            ops.conv3x3_wgrad_splitk(dy16, x16, part, conv[0], conv[1], conv[1], conv[2], kc)
-        else:
-            ops.gemm_tn_splitk(dy16, x16, part, kc)
-        self._reduce(part, s, gw, cout, k)
-        if gb is not None:
-            self._bias_grad(gb, dy16)
-        return True
-
     def _conv1x1_bwd(self, c: _ConvBN, dy16: torch.Tensor, x16: torch.Tensor, need_dx: bool = True) -> Optional[torch.Tensor]:
         m = dy16.shape[0]
-        if not self._wgrad_tn(c.gw, dy16, x16, c.gb):
-            mp = _pad64(m)
-            xt = self._tmp("xt", (c.cin, mp), self.dt, zero=mp != m)
-            ops.transpose16(x16, xt)
-            self._wgrad(c.gw, dy16, xt, m, c.gb)
+        self.wgrad.add(c.gw, dy16, x16, gb=c.gb)
         if not need_dx:
             return None
         dx = torch.empty(m, c.cin, dtype=self.dt, device=self.dev)
@@ -206,13 +129,7 @@ class RNTower:
 
     def _conv3x3_bwd(self, c: _ConvBN, dy16: torch.Tensor, x16: torch.Tensor, b: int, h: int, need_dx: bool = True) -> Optional[torch.Tensor]:
         m = dy16.shape[0]
-        if not self._wgrad_tn(c.gw, dy16, x16, c.gb, conv=(b, h, c.cin)):
-            mp = _pad64(m)
-            xt = self._tmp("xt", (c.cin, mp), self.dt, zero=mp != m)
-            ops.transpose16(x16, xt)
-            col_t = self._tmp("colt", (9 * c.cin, mp), self.dt)
-            ops.im2col3x3_t(xt, col_t, b, h, h)
-            self._wgrad(c.gw, dy16, col_t, m, c.gb)
+        self.wgrad.add(c.gw, dy16, x16, gb=c.gb, conv=(b, h, c.cin))
         if not need_dx:
             return None
         dx = torch.empty(m, c.cin, dtype=self.dt, device=self.dev)
@@ -304,13 +221,9 @@ class RNTower:
         ops.mha_bwd(s["qkv"], s["att"], datt, dqkv, b, l, self.heads, False)
         # in-projection: qkv = tok . Win^T + bin   (q, k, v are separate parameters: scatter the packed gradient)
         m = b * l
-        mp = _pad64(m)
         gwin = self._tmp("gwin", (3 * e, e), torch.float32, zero=True)
         gbin = self._tmp("gbin", (3 * e,), torch.float32, zero=True)
-        if not self._wgrad_tn(gwin, dqkv, s["tok"], gbin):
-            tok_t = self._tmp("xt", (e, mp), dt, zero=mp != m)
-            ops.transpose16(s["tok"], tok_t)
-            self._wgrad(gwin, dqkv, tok_t, m, gbin)
+        self.wgrad.add(gwin, dqkv, s["tok"], gb=gbin)
         for i, lin in enumerate((a.q_proj, a.k_proj, a.v_proj)):
             _grad(lin.weight).add_(gwin[i * e:(i + 1) * e])
             _grad(lin.bias).add_(gbin[i * e:(i + 1) * e])
@@ -354,12 +267,7 @@ class RNTower:
         ops.relu_bwd16(d_a2, s["a2"])
         d_a1 = self._conv3x3_bwd(s2, d_a2, s["a1"], b, hs)
         ops.relu_bwd16(d_a1, s["a1"])
-        m = b * hs * hs
-        mp = _pad64(m)
-        if not self._wgrad_tn(s1.gw, d_a1, s["col"], s1.gb):
-            col_t = self._tmp("xt", (64, mp), dt, zero=mp != m)
-            ops.transpose16(s["col"], col_t)
-            self._wgrad(s1.gw, d_a1, col_t, m, s1.gb)
+        self.wgrad.add(s1.gw, d_a1, s["col"], gb=s1.gb)
         for c in self.stem:
             c.finish()
         for k in self.blocks:

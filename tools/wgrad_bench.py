@@ -8,7 +8,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 
-from hgr_net_amd import _lib, ops
+from hgr_net_amd import _lib, ops, wgrad
 
 m = int(sys.argv[1]) if len(sys.argv) > 1 else 256 * 257
 dt = torch.bfloat16
@@ -29,9 +29,7 @@ for name, na, nb in (("L14 qkv", 3072, 1024), ("L14 out", 1024, 1024), ("L14 fc"
     torch.manual_seed(0)
     p = (torch.randn(m, na, device="cuda") * 0.1).to(dt)
     q = (torch.randn(m, nb, device="cuda") * 0.5).to(dt)
-    s = ops.tn_slices(na, nb, m)
-    kc = (-(-m // s) + 63) // 64 * 64
-    s = -(-m // kc)
+    _, s, kc, _ = wgrad.plan(na, nb, m)
     part = torch.empty(s, na * nb, dtype=torch.float32, device="cuda")
     out = torch.zeros(na * nb, device="cuda")
     scratch = torch.empty(na * nb * 4, device="cuda")

@@ -9,7 +9,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 import torch
 
-from hgr_net_amd import ops
+from hgr_net_amd import ops, wgrad
 DEV="cuda"
 def t(fn,n=10):
     for i in range(2): fn()
@@ -23,7 +23,7 @@ dt=torch.bfloat16
 for (m,n,k,name) in ((65792,3072,1024,"v qkv"),(65792,1024,1024,"v out"),(65792,4096,1024,"v fc"),(65792,1024,4096,"v proj"),
                      (81397,2304,768,"t qkv"),(81397,768,768,"t out"),(81397,3072,768,"t fc"),(81397,768,3072,"t proj")):
     dy=torch.randn(m,n,device=DEV).to(dt); x=torch.randn(m,k,device=DEV).to(dt)
-    s=ops.tn_slices(n,k,m); kc=(-(-m//s)+63)//64*64; s=-(-m//kc)
+    _,s,kc,_=wgrad.plan(n,k,m)
     part=torch.empty(s,n*k,dtype=torch.float32,device=DEV)
     us=t(lambda: ops.gemm_tn_splitk(dy,x,part,kc))
     gw=torch.zeros(n*k,device=DEV); scr=torch.empty(max(1<<22,n*k),device=DEV)
